@@ -86,3 +86,29 @@ def test_valu_insts_tool_follows_the_main_sketch_kernel(tmp_path):
     finally:
         with open(keep, "w") as f:
             f.write(before)
+
+
+def test_dump_outputs_writes_float64_and_samples_past_the_cap(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the last timed step's rows (read x row) and the table as exact float64 .npy files; rows that would take
+    the files past the cap are cut to a fixed, seeded sample of reads, named in sample_reads.npy."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    ti = torch.arange(24, dtype=torch.int32).reshape(12, 2)
+    ts = (torch.arange(24, dtype=torch.int64) + (1 << 40)).reshape(12, 2)
+    table = np.arange(7, dtype=np.uint64) * (1 << 45)
+    bench._dump_outputs(str(tmp_path / "all"), ti, ts, table)
+    got = {n: np.load(tmp_path / "all" / f"{n}.npy") for n in ("topk_idx", "topk_sum", "table")}
+    assert all(a.dtype == np.float64 for a in got.values()) and not (tmp_path / "all" / "sample_reads.npy").exists()
+    assert np.array_equal(got["topk_idx"], ti.numpy()) and np.array_equal(got["topk_sum"], ts.numpy()) and np.array_equal(got["table"], table)
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", table.nbytes + 5 * (16 + 16 + 8))
+    for d in ("a", "b"):
+        bench._dump_outputs(str(tmp_path / d), ti, ts, table)
+    keep = np.load(tmp_path / "a" / "sample_reads.npy").astype(np.int64)
+    assert len(keep) == 5 and np.all(np.diff(keep) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "topk_idx.npy"), ti.numpy()[keep])
+    assert np.array_equal(np.load(tmp_path / "a" / "topk_sum.npy"), ts.numpy()[keep])
+    assert sum(os.path.getsize(tmp_path / "a" / f) - 128 for f in os.listdir(tmp_path / "a")) <= bench.DUMP_CAP_BYTES
+    for f in os.listdir(tmp_path / "a"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f

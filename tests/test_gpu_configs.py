@@ -115,7 +115,7 @@ def _run(cmd, timeout=600, **env):
 
 def _bench_two_ranks(*extra):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--share-gpu", "--config", "c1", "--batch", "8192",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "2", "--share-gpu", "--config", "c1", "--batch", "8192",
                           "--steps", "3", "--warmup", "1", "--reps", "2", "--cpu-seconds", "0", "--no-extra-legs", *extra],
                          capture_output=True, text=True, timeout=900, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT)
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -172,7 +172,7 @@ def test_bench_eight_ranks_on_one_gpu(gpu):
     eight references + eight streams must fit, every rank checks its own shard, rank 0 prints ONE line whose allreduce block
     says which transport summed the table (RCCL refuses ranks that share a device: gloo-host, accepted only by flag)."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--share-gpu", "--allow-host-allreduce", "--config", "c1",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "8", "--share-gpu", "--allow-host-allreduce", "--config", "c1",
                           "--batch", "4096", "--steps", "3", "--warmup", "1", "--reps", "2", "--cpu-seconds", "0", "--no-extra-legs"],
                          capture_output=True, text=True, timeout=1500, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
@@ -191,7 +191,7 @@ def test_bench_eight_ranks_multi_species(gpu, workload_kind):
     eight ranks) at reduced size, all ranks on the box's one GPU: the multi-species path has met eight ranks once.  Every rank
     checks its own shard's rows (4 096-read cuts); rank 0 also compares every row of its first and last step with the oracle."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "8", "--share-gpu", "--allow-host-allreduce", "--config", "c4s",
+    out = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "8", "--share-gpu", "--allow-host-allreduce", "--config", "c4s",
                           "--workload", workload_kind, "--batch", "2048", "--steps", "3", "--warmup", "1", "--reps", "2", "--cpu-seconds", "0",
                           "--no-extra-legs"],
                          capture_output=True, text=True, timeout=1500, env=dict(env, HSA_ENABLE_IPC_MODE_LEGACY="0"), cwd=ROOT)
@@ -209,13 +209,40 @@ def test_bench_multi_species_whole_steps_vs_oracle(gpu):
     against the oracle (orc_stream_fast, one run per species over the mixed stream)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     for kind in ("ancestor", "truth"):
-        out = subprocess.run([sys.executable, "bench.py", "--config", "c4s", "--workload", kind, "--batch", "8192", "--steps", "4", "--warmup", "1",
+        out = subprocess.run([sys.executable, "bench.py", "--full", "--config", "c4s", "--workload", kind, "--batch", "8192", "--steps", "4", "--warmup", "1",
                               "--reps", "2", "--cpu-seconds", "0", "--no-extra-legs"],
                              capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
         j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
         o = j["oracle_whole_steps"]
         assert o["timed_rows_match_oracle"] is True and o["final_table_matches_oracle"] is True and o["rows_compared"] == 2 * 8192 * 5
+
+
+def test_plain_bench_times_its_steps_and_dumps_what_full_checks(gpu, tmp_path):
+    """A plain run: ONE timed region of exactly --steps steps and the line, nothing beside it.  Its --dump-outputs files (the last
+    timed step's rows and the table) are the same from run to run and the same as those of a --full run of the same stream, whose
+    parity and oracle checks pass."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    common = ["--config", "c1", "--batch", "8192", "--steps", "3", "--warmup", "1"]
+    lines = {}
+    for tag, extra in (("a", []), ("b", []), ("full", ["--full", "--reps", "2", "--no-extra-legs", "--cpu-seconds", "0"])):
+        out = subprocess.run([sys.executable, "bench.py", *common, "--dump-outputs", str(tmp_path / tag), *extra],
+                             capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        ls = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(ls) == 1, out.stdout[-2000:]
+        lines[tag] = json.loads(ls[0])
+    j = lines["a"]
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["reps"] == 1 and len(j["values_all"]) == 1 and "parity_error" not in j
+    assert abs(j["value"] - 8192 / (j["ms_per_step"] * 1e-3)) / j["value"] < 1e-6
+    assert not any(k in j for k in ("parity", "roofline", "cpu_baseline", "oracle_whole_steps", "value_cold", "value_ancestor"))
+    f = lines["full"]
+    assert f["reps"] == 2 and all(v is True for v in f["parity"].values()) and f["oracle_whole_steps"]["timed_rows_match_oracle"] is True
+    for name, shape in (("topk_idx", (8192, 1)), ("topk_sum", (8192, 1)), ("table", (5000,))):
+        a = np.load(tmp_path / "a" / f"{name}.npy")
+        assert a.dtype == np.float64 and a.shape == shape, (name, a.dtype, a.shape)
+        for other in ("b", "full"):
+            np.testing.assert_array_equal(a, np.load(tmp_path / other / f"{name}.npy"), err_msg=f"{name}: a vs {other}")
 
 
 def test_comm_watchdog_ends_a_rank_whose_peer_never_arrives(gpu):

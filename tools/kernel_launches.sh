@@ -4,7 +4,7 @@
 TAG=$1; PAT=$2; shift 2
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 P=gpurun_out/prof; mkdir -p $P
-timeout 400 rocprofv3 --kernel-trace --output-format csv -d $P/kl_$TAG -o kt -- python3 bench.py --reps 1 --cpu-seconds 0 --no-extra-legs --no-check "$@" > $P/${TAG}_bench.json 2> $P/${TAG}_bench.err
+timeout 400 rocprofv3 --kernel-trace --output-format csv -d $P/kl_$TAG -o kt -- python3 bench.py --full --reps 1 --cpu-seconds 0 --no-extra-legs --no-check "$@" > $P/${TAG}_bench.json 2> $P/${TAG}_bench.err
 python3 - "$PAT" $(find $P/kl_$TAG -name "*kernel_trace.csv" | head -1) > $P/${TAG}_launches.txt <<'PY'
 import csv, sys
 pats = sys.argv[1].split(",")

@@ -19,7 +19,7 @@ i=0
 : > $P/${TAG}_pmc.csv
 for C in "${PASSES[@]}"; do
   i=$((i+1))
-  timeout 120 env "$@" rocprofv3 --pmc $C --output-format csv -d $P/pmc_${TAG}_$i -o pmc -- python3 bench.py --steps 3 --warmup 1 --cpu-seconds 0 --no-extra-legs --no-check > /dev/null 2> $P/${TAG}_pmc_$i.err || true
+  timeout 120 env "$@" rocprofv3 --pmc $C --output-format csv -d $P/pmc_${TAG}_$i -o pmc -- python3 bench.py --full --steps 3 --warmup 1 --cpu-seconds 0 --no-extra-legs --no-check > /dev/null 2> $P/${TAG}_pmc_$i.err || true
   F=$(find $P/pmc_${TAG}_$i -name "*counter_collection.csv" | head -1)
   if [ -n "$F" ]; then python3 profiles/summarize_pmc.py $F | grep -E "$KPAT" >> $P/${TAG}_pmc.csv || true; fi
   rm -rf $P/pmc_${TAG}_$i

@@ -6,7 +6,7 @@
 TAG=$1
 cd /tmp && export TMPDIR=/tmp; cd "$GRAFT_REPO_ROOT"
 P=gpurun_out/prof; mkdir -p $P
-{ echo "== rocprofv3 --att attempt"; ls /opt/rocm/lib | grep -i -E "decoder|att" ; timeout 200 rocprofv3 --att --att-target-cu 1 --kernel-include-regex "sketch_wave_kernel" --output-format csv -d $P/att_$TAG -o att -- python3 bench.py --steps 2 --warmup 0 --reps 1 --cpu-seconds 0 --no-extra-legs --no-check 2>&1 | grep -v "^{" | tail -15; echo "rc=$?"; find $P/att_$TAG -type f 2>/dev/null | head -20; } > $P/${TAG}_att_attempt.txt 2>&1
+{ echo "== rocprofv3 --att attempt"; ls /opt/rocm/lib | grep -i -E "decoder|att" ; timeout 200 rocprofv3 --att --att-target-cu 1 --kernel-include-regex "sketch_wave_kernel" --output-format csv -d $P/att_$TAG -o att -- python3 bench.py --full --steps 2 --warmup 0 --reps 1 --cpu-seconds 0 --no-extra-legs --no-check 2>&1 | grep -v "^{" | tail -15; echo "rc=$?"; find $P/att_$TAG -type f 2>/dev/null | head -20; } > $P/${TAG}_att_attempt.txt 2>&1
 rm -rf $P/att_$TAG
 cat $P/${TAG}_att_attempt.txt | tail -25
 tools/pmc_sketch.sh ${TAG}_sketch > /dev/null 2>&1

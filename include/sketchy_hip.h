@@ -20,6 +20,8 @@
  *   skx_common_hashes      <- Sketchy::_common_hashes (src/sketchy.rs:419-459) for sketch
  *                             collections (the `shared` all-pairs use at :251-261)
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
+ *   skx_sketch_groups      <- finch SketchScheme::{process x many, to_vec}: ONE sketcher fed several records -- all reads of an
+ *                             offline `predict` (src/sketchy.rs:291-302), all contigs of a genome file in `sketch` (:473-478)
  *
  * Conventions: every function returns 0 (SKX_OK) or a negative SKX_ERR_* code and never
  * throws; skx_last_error() returns a thread-local message for the last failure.  Handles
@@ -306,6 +308,15 @@ int skx_stream_scan_alone(skx_stream *st, uint32_t reps, double *ms_avg);
 /* sketch n_reads reads with (k, seed, s); outputs as in skx_stream_push (host arrays) */
 int skx_sketch_reads(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t *bases,
                      const uint64_t *offsets, uint32_t n_reads, uint64_t *sketches, uint32_t *sketch_len);
+/* finch SketchScheme::{process x many, to_vec}: ONE sketcher per group of records (src/sketchy.rs:291-302, :473-478).
+ * Group g = records [group_first[g], group_first[g+1]); group_first[0] = 0, group_first[n_groups] = n_records, non-decreasing.
+ * sketches [n_groups][s] ascending distinct, zero-padded; sketch_len [n_groups];
+ * valid_kmers [n_groups] (optional, NULL to skip): windows of k bases that are all A/C/G/T/U after normalisation, duplicates counted.
+ * The per-record rows never leave the device: they are reduced there (a segmented merge tree) and n_groups x s hashes
+ * come back.  Any number of records: beyond 2 GiB of per-record rows (or 1 GiB of bases) the call works in slices. */
+int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t *bases, const uint64_t *offsets,
+                      uint32_t n_records, const uint32_t *group_first, uint32_t n_groups,
+                      uint64_t *sketches, uint32_t *sketch_len, uint64_t *valid_kmers);
 /*
  * common[q][g] = |query sketch q  intersect  reference genome g|  (src/sketchy.rs:419-438) for
  * n_query ascending sketches laid out like skx_ref_create's input (row stride q_stride).

@@ -65,6 +65,7 @@ SYMBOLS = [
     ("skx_stream_profile", _i, [_vp, C.POINTER(C.c_double), C.POINTER(_u64)]),
     ("skx_stream_scan_alone", _i, [_vp, C.c_uint32, C.POINTER(C.c_double)]),
     ("skx_sketch_reads", _i, [_i, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
+    ("skx_sketch_groups", _i, [_i, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     ("skx_common_hashes", _i, [_vp, _vp, _vp, _u32, _u32, _vp]),
     ("skx_comm_unique_id", _i, [_vp]),
     ("skx_comm_create", _i, [_pp, _i, _i, _i, _vp]),

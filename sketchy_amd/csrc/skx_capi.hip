@@ -3739,6 +3739,198 @@ SKX_API int skx_sketch_reads(int device, uint32_t k, uint64_t seed, uint32_t s, 
     return rc;
 }
 
+// ---- pooled sketches: one sketcher per group of records
+// The per-record rows (two buffers of the merge tree) take at most kPoolRowBytes of device memory and a slice's bases at most
+// kPoolBaseBytes (one record is never cut); records beyond that are processed in slices.  Groups are runs of consecutive
+// records, so at most ONE group is open across a slice boundary: its partial pooled row waits in `acc` and is merged with the
+// root of the group's rows in the next slice.  Pooled rows leave in chunks of at most kPoolOutBytes.
+static const u64 kPoolRowBytes = 2ull << 30, kPoolBaseBytes = 1ull << 30, kPoolOutBytes = 256ull << 20;
+namespace {
+struct DevMem {  // a device allocation that grows on demand and is freed on every way out of the scope
+    void* p = nullptr; size_t cap = 0;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    hipError_t need(size_t bytes) {
+        if (bytes <= cap && p) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+}  // namespace
+static u32 ceil_log2(u32 n) { u32 r = 0; while (r < 32 && (1ull << r) < n) ++r; return r; }
+
+SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases, const uint64_t* offsets,
+                              uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
+                              uint32_t* sketch_len, uint64_t* valid_kmers) {
+    if (!offsets) return fail(SKX_ERR_INVALID, "skx_sketch_groups: offsets is NULL");
+    if (!group_first) return fail(SKX_ERR_INVALID, "skx_sketch_groups: group_first is NULL");
+    if (!sketches) return fail(SKX_ERR_INVALID, "skx_sketch_groups: sketches is NULL");
+    if (!sketch_len) return fail(SKX_ERR_INVALID, "skx_sketch_groups: sketch_len is NULL");
+    if (k < 1 || k > SKX_MAX_K) return fail(SKX_ERR_INVALID, "skx_sketch_groups: k = %u outside 1..%u", k, SKX_MAX_K);
+    if (s < 1) return fail(SKX_ERR_INVALID, "skx_sketch_groups: s must be at least 1");
+    u64 longest = 1;
+    for (u32 r = 0; r < n_records; ++r) {
+        if (offsets[r + 1] < offsets[r]) return fail(SKX_ERR_INVALID, "skx_sketch_groups: offsets not monotonic at record %u", r);
+        longest = std::max<u64>(longest, offsets[r + 1] - offsets[r]);
+    }
+    if (group_first[0] != 0) return fail(SKX_ERR_INVALID, "skx_sketch_groups: group_first[0] must be 0");
+    for (u32 g = 0; g < n_groups; ++g)
+        if (group_first[g + 1] < group_first[g]) return fail(SKX_ERR_INVALID, "skx_sketch_groups: group_first decreases at group %u", g);
+    if (group_first[n_groups] != n_records)
+        return fail(SKX_ERR_INVALID, "skx_sketch_groups: group_first[n_groups] = %u must be n_records = %u", group_first[n_groups], n_records);
+    if (n_records && offsets[n_records] > offsets[0] && !bases) return fail(SKX_ERR_INVALID, "skx_sketch_groups: bases is NULL");
+    if (n_groups == 0) return SKX_OK;
+    SKXCHK(use_device(device));
+    if (valid_kmers) memset(valid_kmers, 0, (size_t)n_groups * 8);
+    if (n_records == 0) {  // every group is empty
+        memset(sketches, 0, (size_t)n_groups * s * 8);
+        memset(sketch_len, 0, (size_t)n_groups * 4);
+        return SKX_OK;
+    }
+    const u32 stride = (u32)std::min<u64>(s, longest);
+    u64 rows_cap = std::max<u64>(1, kPoolRowBytes / (2ull * stride * 8));
+#ifdef SKX_EXPERIMENTS
+    if (const char* e = skx::knob("SKX_POOL_ROWS")) rows_cap = std::max<u64>(1, strtoull(e, nullptr, 10));  // (tests: slicing at toy size)
+#endif
+    const u32 out_cap = (u32)std::min<u64>(n_groups, std::max<u64>(1, kPoolOutBytes / ((u64)s * 8)));
+
+    DevMem m_b, m_o, m_sk[2], m_len[2], m_cnt, m_lists, m_vk, m_items, m_desc, m_out, m_out_len, m_acc[2], m_acc_len, m_seg, m_seg_sum;
+    std::vector<u64> off;
+    std::vector<uint2> items, desc, segs;
+    std::vector<u32> round_at, seg_group;
+    std::vector<u64> seg_sum;
+    hipError_t e = hipSuccess;
+    int rc = SKX_OK;
+    u32 r0 = 0, g_out = 0;  // next record; next group whose row has not left yet
+    bool carry = false;     // group g_out has a partial row in acc[cur]
+    int cur = 0;
+#define SKX_TRY(expr) if ((e = (expr)) != hipSuccess) break
+    do {
+        SKX_TRY(m_acc[0].need((size_t)s * 8));
+        SKX_TRY(m_acc[1].need((size_t)s * 8));
+        SKX_TRY(m_acc_len.need(2 * 4));
+        SKX_TRY(m_out.need((size_t)out_cap * s * 8));
+        SKX_TRY(m_out_len.need((size_t)out_cap * 4));
+        SKX_TRY(m_desc.need((size_t)out_cap * sizeof(uint2)));
+        while (r0 < n_records && e == hipSuccess) {
+            // ---- the slice: records [r0, r1)
+            u32 r1 = r0;
+            while (r1 < n_records && r1 - r0 < rows_cap && (r1 == r0 || offsets[r1 + 1] - offsets[r0] <= kPoolBaseBytes)) ++r1;
+            const u32 n = r1 - r0;
+            const u64 n_bases = offsets[r1] - offsets[r0];
+            off.resize((size_t)n + 1);
+            for (u32 r = 0; r <= n; ++r) off[r] = offsets[r0 + r] - offsets[r0];
+            SKX_TRY(m_b.need(std::max<u64>(n_bases, 1)));
+            SKX_TRY(m_o.need(((size_t)n + 1) * 8));
+            for (int i = 0; i < 2; ++i) { SKX_TRY(m_sk[i].need((size_t)n * stride * 8)); SKX_TRY(m_len[i].need((size_t)n * 4)); }
+            if (e != hipSuccess) break;
+            SKX_TRY(m_cnt.need((size_t)n * 4));
+            SKX_TRY(m_lists.need(2 * ((size_t)n + 1) * 4));
+            if (n_bases) SKX_TRY(hipMemcpy(m_b.p, bases + offsets[r0], n_bases, hipMemcpyHostToDevice));
+            SKX_TRY(hipMemcpy(m_o.p, off.data(), ((size_t)n + 1) * 8, hipMemcpyHostToDevice));
+            SKX_TRY(hipMemset(m_lists.p, 0, 2 * ((size_t)n + 1) * 4));
+            // ---- stage A: one ascending distinct row per record, exactly as skx_sketch_reads
+            u32* d_lists = m_lists.as<u32>();
+            SKX_TRY(skx::launch_sketch(nullptr, m_b.as<uint8_t>(), m_o.as<u64>(), n, k, seed, s, 0, false, m_sk[0].as<u64>(), stride,
+                                       m_len[0].as<u32>(), m_cnt.as<u32>(), nullptr, 0, d_lists, d_lists + n + 1, n_bases, nullptr, 0));
+            u32 n_big = 0;
+            SKX_TRY(hipMemcpy(&n_big, d_lists + n + 1, 4, hipMemcpyDeviceToHost));
+            SKX_TRY(skx::launch_sketch_block(nullptr, m_b.as<uint8_t>(), m_o.as<u64>(), d_lists + n + 1, n_big, k, seed, s, 0, false,
+                                             m_sk[0].as<u64>(), stride, m_len[0].as<u32>(), m_cnt.as<u32>(), nullptr, 0));
+            // ---- the groups of the slice: [g_out, g_end) end in it, group g_end (if it has records here) stays open
+            u32 g_end = g_out;
+            while (g_end < n_groups && group_first[g_end + 1] <= r1) ++g_end;
+            const bool open = g_end < n_groups && group_first[g_end] < r1;
+            segs.clear(); seg_group.clear();
+            u32 max_rows = 0;
+            for (u32 g = g_out; g < g_end + (open ? 1u : 0u); ++g) {
+                const u32 a = std::max(group_first[g], r0), b = std::min(group_first[g + 1], r1);
+                if (b > a) { segs.push_back(make_uint2(a - r0, b - a)); seg_group.push_back(g); max_rows = std::max(max_rows, b - a); }
+            }
+            // ---- stage B: the merge tree, round by round
+            const u32 n_rounds = ceil_log2(max_rows);
+            items.clear(); round_at.assign(1, 0);
+            for (u32 r = 0; r < n_rounds; ++r) {
+                const u64 half = 1ull << r;
+                for (const uint2& sg : segs)
+                    if (sg.y > half)
+                        for (u64 j = 0; j < sg.y; j += 2 * half)
+                            items.push_back(make_uint2(sg.x + (u32)j, j + half < sg.y ? sg.x + (u32)(j + half) : 0xFFFFFFFFu));
+                round_at.push_back((u32)items.size());
+            }
+            if (!items.empty()) {
+                SKX_TRY(m_items.need(items.size() * sizeof(uint2)));
+                SKX_TRY(hipMemcpy(m_items.p, items.data(), items.size() * sizeof(uint2), hipMemcpyHostToDevice));
+                for (u32 r = 0; r < n_rounds; ++r)
+                    skx::launch_pool_merge_round(nullptr, m_items.as<uint2>() + round_at[r], round_at[r + 1] - round_at[r], m_sk[r & 1].as<u64>(),
+                                                 m_len[r & 1].as<u32>(), m_sk[(r + 1) & 1].as<u64>(), m_len[(r + 1) & 1].as<u32>(), stride, s);
+                SKX_TRY(hipGetLastError());
+            }
+            auto root = [&](const uint2& sg, const u64** row, const u32** len) {
+                const u32 par = ceil_log2(sg.y) & 1u;
+                *row = m_sk[par].as<u64>() + (size_t)sg.x * stride; *len = m_len[par].as<u32>() + sg.x;
+            };
+            u32* acc_len = m_acc_len.as<u32>();
+            // the open group of the slice before: its partial row + the root of its rows here (always the first segment)
+            if (carry) {
+                const u64* row; const u32* len;
+                root(segs[0], &row, &len);
+                skx::launch_pool_merge_one(nullptr, m_acc[cur].as<u64>(), acc_len + cur, row, len, m_acc[cur ^ 1].as<u64>(), acc_len + (cur ^ 1), s);
+                cur ^= 1;
+            }
+            // ---- valid k-mers: per record, then per segment
+            if (valid_kmers && !segs.empty()) {
+                SKX_TRY(m_vk.need((size_t)n * 8));
+                SKX_TRY(m_seg.need(segs.size() * sizeof(uint2)));
+                SKX_TRY(m_seg_sum.need(segs.size() * 8));
+                SKX_TRY(hipMemcpy(m_seg.p, segs.data(), segs.size() * sizeof(uint2), hipMemcpyHostToDevice));
+                skx::launch_pool_valid_kmers(nullptr, m_b.as<uint8_t>(), m_o.as<u64>(), n, k, m_vk.as<u64>());
+                skx::launch_pool_seg_sum(nullptr, m_vk.as<u64>(), m_seg.as<uint2>(), (u32)segs.size(), m_seg_sum.as<u64>());
+                seg_sum.resize(segs.size());
+                SKX_TRY(hipMemcpy(seg_sum.data(), m_seg_sum.p, segs.size() * 8, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < segs.size(); ++i) valid_kmers[seg_group[i]] += seg_sum[i];
+            }
+            // ---- the rows of the groups that end here, out_cap at a time
+            size_t si = 0;  // next segment
+            for (u32 g = g_out; g < g_end && e == hipSuccess; g += out_cap) {
+                const u32 cnt = std::min(out_cap, g_end - g);
+                desc.assign(cnt, make_uint2(0, 0));
+                for (u32 i = 0; i < cnt; ++i) {
+                    while (si < segs.size() && seg_group[si] < g + i) ++si;
+                    if (si < segs.size() && seg_group[si] == g + i) desc[i] = (carry && g + i == g_out) ? make_uint2(0xFFFFFFFFu, 1u) : segs[si];
+                }
+                SKX_TRY(hipMemcpy(m_desc.p, desc.data(), (size_t)cnt * sizeof(uint2), hipMemcpyHostToDevice));
+                skx::launch_pool_gather(nullptr, m_desc.as<uint2>(), cnt, m_sk[0].as<u64>(), m_sk[1].as<u64>(), m_len[0].as<u32>(), m_len[1].as<u32>(),
+                                        stride, m_acc[cur].as<u64>(), acc_len + cur, m_out.as<u64>(), m_out_len.as<u32>(), s);
+                SKX_TRY(hipGetLastError());
+                SKX_TRY(hipMemcpy(sketches + (size_t)g * s, m_out.p, (size_t)cnt * s * 8, hipMemcpyDeviceToHost));
+                SKX_TRY(hipMemcpy(sketch_len + g, m_out_len.p, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+            }
+            if (e != hipSuccess) break;
+            // ---- the group that stays open: its row so far waits in acc
+            if (open) {
+                if (!(carry && g_end == g_out)) {  // (else: merged into acc above)
+                    const u64* row; const u32* len;
+                    root(segs.back(), &row, &len);
+                    SKX_TRY(hipMemcpy(acc_len + cur, len, 4, hipMemcpyDeviceToDevice));
+                    SKX_TRY(hipMemcpy(m_acc[cur].p, row, (size_t)std::min<u64>(s, (u64)segs.back().y * stride) * 8, hipMemcpyDeviceToDevice));
+                }
+                carry = true;
+            } else {
+                carry = false;
+            }
+            SKX_TRY(hipDeviceSynchronize());  // (the next slice reuses every buffer)
+            g_out = g_end;
+            r0 = r1;
+        }
+    } while (0);
+#undef SKX_TRY
+    if (e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_sketch_groups: %s", hipGetErrorString(e));
+    return rc;
+}
+
 SKX_API int skx_common_hashes(const skx_ref* ref, const uint64_t* query, const uint32_t* query_len, uint32_t n_query,
                               uint32_t q_stride, uint32_t* common) {
     if (!ref || !query || !query_len || !common) return fail(SKX_ERR_INVALID, "NULL argument");

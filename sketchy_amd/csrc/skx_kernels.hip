@@ -5644,6 +5644,187 @@ void launch_gather_table(hipStream_t st, const u64* cum, u64* out, u32 n_real, c
     hipLaunchKernelGGL(gather_table_kernel, dim3(cdiv(n_real, 256)), dim3(256), 0, st, cum, out, n_real, real2pad);
 }
 
+// =====================================================================================
+// pooled sketches: one bottom-s sketch per GROUP of records (skx_sketch_groups)
+// =====================================================================================
+// The sketchers leave one ascending distinct row per record (row r at r * stride, stride = min(s, longest record): a record
+// has fewer hashes than bases).  A group's pooled sketch is the s smallest distinct values of the union of its rows: a
+// segmented pairwise merge tree over two buffers of the same geometry.  Round r merges, inside every group, the rows 2^r
+// apart; the result of the subtree rooted at row i may use the slots of ALL rows of the subtree (they are contiguous and dead
+// in the destination buffer), so a merged row of up to s entries needs no wider slot than a leaf.  Every live row of a group
+// that still has a merge ahead moves to the other buffer in every round (a row without a partner is copied), which is what
+// keeps the destination span dead; after ceil(log2(rows)) rounds the group's first row is its pooled sketch, in buffer
+// (rounds & 1).
+//
+// One workgroup per pair: tiles of 256 merged elements through LDS, one merge-path diagonal per lane (binary search over the
+// two windows), an element equal to its predecessor in merged order is dropped (rows are strictly ascending: a value occurs
+// at most twice, the copy from A first), survivors are compacted with a ballot prefix per wave + the waves' counts in LDS,
+// coalesced 8-byte stores, the running count stops the walk at s.  Work: at most 2 s element steps per pair.
+constexpr u32 kPoolTile = 256;       // = threads of the workgroup
+struct PoolLds { u64 a[kPoolTile]; u64 b[kPoolTile]; u32 wave_cnt[4]; u32 used_a; u64 last; };
+
+__device__ __forceinline__ u32 pool_merge_rows(PoolLds& L, const u64* __restrict__ A, u32 na, const u64* __restrict__ B, u32 nb,
+                                               u64* __restrict__ dst, u32 s) {
+    const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    u32 a0 = 0, b0 = 0, outn = 0;
+    u64 last = 0;
+    bool has_last = false;
+    while (outn < s && (a0 < na || b0 < nb)) {  // (block-uniform)
+        const u32 ca = min(kPoolTile, na - a0), cb = min(kPoolTile, nb - b0);
+        const u32 total = min(kPoolTile, ca + cb);  // the next `total` merged elements lie inside the two windows
+        __syncthreads();
+        if (tid < ca) L.a[tid] = A[a0 + tid];
+        if (tid < cb) L.b[tid] = B[b0 + tid];
+        __syncthreads();
+        bool keep = false;
+        u64 v = 0;
+        if (tid < total) {
+            // i = elements of A among the first `tid` merged ones (ties: A first)
+            u32 lo = tid > cb ? tid - cb : 0u, hi = min(tid, ca);
+            while (lo < hi) {
+                const u32 mid = (lo + hi) >> 1;
+                if (L.a[mid] <= L.b[tid - 1u - mid]) lo = mid + 1u; else hi = mid;
+            }
+            const u32 i = lo, j = tid - lo;
+            const bool from_a = j >= cb || (i < ca && L.a[i] <= L.b[j]);
+            v = from_a ? L.a[i] : L.b[j];
+            u64 pred = last;
+            bool has_pred = has_last;
+            if (tid > 0u) {
+                has_pred = true;
+                pred = 0;
+                if (i > 0u) pred = L.a[i - 1u];
+                if (j > 0u) pred = max(pred, L.b[j - 1u]);
+            }
+            keep = !(has_pred && pred == v);
+            if (tid == total - 1u) { L.used_a = i + (from_a ? 1u : 0u); L.last = v; }
+        }
+        const u64 km = __ballot(keep);
+        if (lane == 0u) L.wave_cnt[wave] = (u32)__popcll(km);
+        __syncthreads();
+        u32 before = 0, all = 0;
+#pragma unroll
+        for (u32 w = 0; w < 4u; ++w) { const u32 c = L.wave_cnt[w]; before += w < wave ? c : 0u; all += c; }
+        const u32 pos = outn + before + (u32)__popcll(km & lanemask_lt());
+        if (keep && pos < s) dst[pos] = v;
+        outn += all;
+        const u32 ua = L.used_a;
+        a0 += ua; b0 += total - ua;
+        last = L.last; has_last = true;
+    }
+    return min(outn, s);
+}
+
+// items[i] = {left row, partner row or 0xFFFFFFFF}: dst row `left` = merge (or copy) of the src rows
+__global__ __launch_bounds__(256) void pool_merge_round_kernel(const uint2* __restrict__ items, const u64* __restrict__ src,
+                                                               const u32* __restrict__ src_len, u64* __restrict__ dst,
+                                                               u32* __restrict__ dst_len, u32 stride, u32 s) {
+    __shared__ PoolLds L;
+    const uint2 it = items[blockIdx.x];
+    const u64* A = src + (size_t)it.x * stride;
+    u64* out = dst + (size_t)it.x * stride;
+    const u32 na = min(src_len[it.x], s);
+    if (it.y == 0xFFFFFFFFu) {
+        for (u32 i = threadIdx.x; i < na; i += blockDim.x) out[i] = A[i];
+        if (threadIdx.x == 0u) dst_len[it.x] = na;
+        return;
+    }
+    const u32 n = pool_merge_rows(L, A, na, src + (size_t)it.y * stride, min(src_len[it.y], s), out, s);
+    if (threadIdx.x == 0u) dst_len[it.x] = n;
+}
+// one pair given by pointers: a group's partial row carried over from the slice before + the root of its rows in this slice
+__global__ __launch_bounds__(256) void pool_merge_one_kernel(const u64* __restrict__ A, const u32* __restrict__ na, const u64* __restrict__ B,
+                                                             const u32* __restrict__ nb, u64* __restrict__ dst, u32* __restrict__ dst_len, u32 s) {
+    __shared__ PoolLds L;
+    const u32 n = pool_merge_rows(L, A, min(*na, s), B, min(*nb, s), dst, s);
+    if (threadIdx.x == 0u) *dst_len = n;
+}
+__device__ __forceinline__ u32 pool_rounds(u32 rows) { return rows <= 1u ? 0u : 32u - (u32)__clz(rows - 1u); }  // ceil(log2(rows))
+// desc[g] = {first row of the group's rows in the buffers, number of rows}; rows = 0: an empty group; first row = 0xFFFFFFFF: the
+// group's row is `acc`.  out[g][s] zero-padded, out_len[g].
+__global__ __launch_bounds__(256) void pool_gather_kernel(const uint2* __restrict__ desc, const u64* __restrict__ buf0, const u64* __restrict__ buf1,
+                                                          const u32* __restrict__ len0, const u32* __restrict__ len1, u32 stride,
+                                                          const u64* __restrict__ acc, const u32* __restrict__ acc_len, u64* __restrict__ out,
+                                                          u32* __restrict__ out_len, u32 s) {
+    const uint2 d = desc[blockIdx.x];
+    const u64* src = nullptr;
+    u32 n = 0;
+    if (d.x == 0xFFFFFFFFu) { src = acc; n = *acc_len; }
+    else if (d.y != 0u) {
+        const bool odd = (pool_rounds(d.y) & 1u) != 0u;
+        src = (odd ? buf1 : buf0) + (size_t)d.x * stride;
+        n = (odd ? len1 : len0)[d.x];
+    }
+    n = min(n, s);
+    u64* o = out + (size_t)blockIdx.x * s;
+    for (u32 i = threadIdx.x; i < s; i += blockDim.x) o[i] = i < n ? src[i] : 0ull;
+    if (threadIdx.x == 0u) out_len[blockIdx.x] = n;
+}
+// windows of k retained bases that are all A/C/G/T/U per record (whitespace is removed, any other byte breaks the run: the
+// sketchers' normalisation, classify_base), duplicates counted.  One workgroup per record; a thread takes a contiguous chunk and
+// first walks back over at most k - 1 retained bases to learn the run it starts in.
+__global__ __launch_bounds__(256) void pool_valid_kmers_kernel(const uint8_t* __restrict__ bases, const u64* __restrict__ offsets, u32 k,
+                                                               u64* __restrict__ valid) {
+    __shared__ u64 part[4];
+    const u32 r = blockIdx.x;
+    const u64 b0 = offsets[r], len = offsets[r + 1u] - b0;
+    const u64 chunk = max((u64)64, (len + blockDim.x - 1u) / blockDim.x);
+    const u64 c0 = min(len, (u64)threadIdx.x * chunk), c1 = min(len, c0 + chunk);
+    u64 n = 0;
+    if (c0 < c1) {
+        u32 run = 0;
+        for (u64 p = c0; p > 0u && run < k - 1u; --p) {
+            const u32 c = classify_base(bases[b0 + p - 1u]);
+            if (c == 5u) continue;
+            if (c > 3u) break;
+            ++run;
+        }
+        for (u64 p = c0; p < c1; ++p) {
+            const u32 c = classify_base(bases[b0 + p]);
+            if (c == 5u) continue;
+            run = c > 3u ? 0u : min(run + 1u, k);
+            n += run >= k ? 1u : 0u;
+        }
+    }
+    for (int m = 32; m > 0; m >>= 1) n += shfl_xor64(n, m);
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0u) valid[r] = part[0] + part[1] + part[2] + part[3];
+}
+// out[i] = sum of v[seg[i].x .. seg[i].x + seg[i].y)
+__global__ __launch_bounds__(256) void pool_seg_sum_kernel(const u64* __restrict__ v, const uint2* __restrict__ seg, u64* __restrict__ out) {
+    __shared__ u64 part[4];
+    const uint2 sg = seg[blockIdx.x];
+    u64 n = 0;
+    for (u32 i = threadIdx.x; i < sg.y; i += blockDim.x) n += v[(size_t)sg.x + i];
+    for (int m = 32; m > 0; m >>= 1) n += shfl_xor64(n, m);
+    if ((threadIdx.x & 63u) == 0u) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0u) out[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+void launch_pool_merge_round(hipStream_t st, const uint2* items, u32 n_items, const u64* src, const u32* src_len, u64* dst, u32* dst_len,
+                             u32 stride, u32 s) {
+    if (n_items == 0) return;
+    hipLaunchKernelGGL(pool_merge_round_kernel, dim3(n_items), dim3(256), 0, st, items, src, src_len, dst, dst_len, stride, s);
+}
+void launch_pool_merge_one(hipStream_t st, const u64* a, const u32* na, const u64* b, const u32* nb, u64* dst, u32* dst_len, u32 s) {
+    hipLaunchKernelGGL(pool_merge_one_kernel, dim3(1), dim3(256), 0, st, a, na, b, nb, dst, dst_len, s);
+}
+void launch_pool_gather(hipStream_t st, const uint2* desc, u32 n_groups, const u64* buf0, const u64* buf1, const u32* len0, const u32* len1,
+                        u32 stride, const u64* acc, const u32* acc_len, u64* out, u32* out_len, u32 s) {
+    if (n_groups == 0) return;
+    hipLaunchKernelGGL(pool_gather_kernel, dim3(n_groups), dim3(256), 0, st, desc, buf0, buf1, len0, len1, stride, acc, acc_len, out, out_len, s);
+}
+void launch_pool_valid_kmers(hipStream_t st, const uint8_t* bases, const u64* offsets, u32 n_records, u32 k, u64* valid) {
+    if (n_records == 0) return;
+    hipLaunchKernelGGL(pool_valid_kmers_kernel, dim3(n_records), dim3(256), 0, st, bases, offsets, k, valid);
+}
+void launch_pool_seg_sum(hipStream_t st, const u64* v, const uint2* seg, u32 n_seg, u64* out) {
+    if (n_seg == 0) return;
+    hipLaunchKernelGGL(pool_seg_sum_kernel, dim3(n_seg), dim3(256), 0, st, v, seg, out);
+}
+
 }  // namespace skx
 
 #ifdef SKX_EXPERIMENTS

@@ -345,4 +345,21 @@ void launch_shared_debug(hipStream_t st, const u32* pair_q, const u32* poff, u32
 void launch_add_table(hipStream_t st, u64* cum, const u64* add, u32 n_real, const u32* real2pad);
 void launch_gather_table(hipStream_t st, const u64* cum, u64* out, u32 n_real, const u32* real2pad);
 
+// ---- pooled sketches (skx_kernels.hip, "pooled sketches"): the bottom-s distinct hashes of the union of a group's rows
+// One round of the segmented merge tree: items[i] = {left row, partner row or 0xFFFFFFFF (no partner: the row is copied)}; rows are
+// `stride` entries apart in src / dst (two buffers of the same geometry), lengths in src_len / dst_len; dst row `left` receives at
+// most s values and may extend over the slots of the rows of its subtree.
+void launch_pool_merge_round(hipStream_t st, const uint2* items, u32 n_items, const u64* src, const u32* src_len, u64* dst, u32* dst_len,
+                             u32 stride, u32 s);
+// dst[0 .. *dst_len) = first s distinct values of a[0 .. *na) U b[0 .. *nb) (ascending rows, device lengths)
+void launch_pool_merge_one(hipStream_t st, const u64* a, const u32* na, const u64* b, const u32* nb, u64* dst, u32* dst_len, u32 s);
+// out[g][s] (zero-padded), out_len[g] for n_groups groups: desc[g] = {first row, rows} -- the pooled row of a group of `rows` rows sits
+// at its first row in buffer (ceil(log2(rows)) & 1); rows = 0: empty group; first row = 0xFFFFFFFF: the row is acc[0 .. *acc_len)
+void launch_pool_gather(hipStream_t st, const uint2* desc, u32 n_groups, const u64* buf0, const u64* buf1, const u32* len0, const u32* len1,
+                        u32 stride, const u64* acc, const u32* acc_len, u64* out, u32* out_len, u32 s);
+// valid[r] = windows of k retained bases of record r that are all A/C/G/T/U (the sketchers' normalisation), duplicates counted
+void launch_pool_valid_kmers(hipStream_t st, const uint8_t* bases, const u64* offsets, u32 n_records, u32 k, u64* valid);
+// out[i] = sum of v[seg[i].x .. seg[i].x + seg[i].y)
+void launch_pool_seg_sum(hipStream_t st, const u64* v, const uint2* seg, u32 n_seg, u64* out);
+
 }  // namespace skx

@@ -4,12 +4,12 @@
 //   sketchy::PredictConfig            src/sketchy.rs:43-50
 //   Sketchy::predict                  src/sketchy.rs:66-124   (reference + genotypes + FASTX, header line, mode switch)
 //   Sketchy::_sum_of_shared_hashes    src/sketchy.rs:317-356  (streaming: rows after every read)  -> skx_stream_push
-//   Sketchy::_shared_hashes           src/sketchy.rs:281-315  (offline: one pooled sketch)         -> skx_sketch_reads + skx_common_hashes
+//   Sketchy::_shared_hashes           src/sketchy.rs:281-315  (offline: one pooled sketch)         -> skx_sketch_groups + skx_common_hashes
 //   Sketchy::_print_results           src/sketchy.rs:358-402  (rows / consensus)
 //   Sketchy::shared                   src/sketchy.rs:238-279                                       -> skx_common_hashes
 //   Sketchy::info (names only)        src/sketchy.rs:172-208
 //   Sketchy::check                    src/sketchy.rs:212-236
-//   Sketchy::sketch + _sketch_files   src/sketchy.rs:128-167, :465-494  (genome files -> Mash .msh)      -> skx_sketch_reads
+//   Sketchy::sketch + _sketch_files   src/sketchy.rs:128-167, :465-494  (genome files -> Mash .msh)      -> skx_sketch_groups
 // Command line: the reference's flag names and defaults (src/cli.rs:25-132).
 //
 // Streaming (`predict -s`) runs as a pipeline of four stages (the reference reads, scores and prints one record at a time
@@ -39,6 +39,12 @@
 
 #include "formats.hpp"
 #include "sketchy_hip.h"
+
+// The pooled entry point is referenced WEAKLY: a library without it (the stub of the sanitizer build, tests/stub) leaves the
+// address null and the host pools the per-record rows of skx_sketch_reads itself; libsketchy_hip.so always has it.
+extern "C" int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases, const uint64_t* offsets,
+                                 uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
+                                 uint32_t* sketch_len, uint64_t* valid_kmers) __attribute__((weak));
 
 namespace sketchy {
 
@@ -112,54 +118,67 @@ class Sketchy {
     }
 
     // `sketchy sketch` (src/sketchy.rs:128-167; _sketch_files :465-494): one Mash sketch per input FILE over all of its
-    // records (k-mers never span records), name = file name (:484).  Every record is sketched on the device
-    // (skx_sketch_reads: genomes take the block-per-read + segmented-sort path); the bottom-s of a file is the
-    // bottom-s of the union of its records' bottom-s sketches, merged here.
+    // records (k-mers never span records), name = file name (:484).  Whole files are batched, several per call, one group of
+    // records per file: the device sketches every record (genomes take the block-per-read + segmented-sort path), pools the
+    // rows of a group and counts its valid k-mers (skx_sketch_groups) -- one row of s hashes per file comes back.  A file
+    // larger than a batch is cut at record boundaries and its per-batch rows are merged here.
     void sketch(const std::vector<std::string>& files, const std::string& output, size_t sketch_size, uint32_t kmer, uint64_t seed) {
         const auto dot = output.rfind('.');
         const std::string ext = dot == std::string::npos ? "" : output.substr(dot + 1);
         if (ext == "fsh") throw SketchyError("Finch scaled sketches (.fsh) are outside the accelerated path");
         if (ext != "msh") throw SketchyError("output sketch file must have Mash (.msh) or Finch (.fsh) extension");  // :573-600
         if (sketch_size < 1) throw SketchyError("sketch size must be at least 1");
+        if (sketch_size > 0xFFFFFFFFull) throw SketchyError("sketch size must fit 32 bits");
         if (kmer < 1 || kmer > SKX_MAX_K) throw SketchyError("k-mer size must be between 1 and " + std::to_string(SKX_MAX_K));
         if (seed > 0xFFFFFFFFull) throw SketchyError("the Mash format stores a 32-bit hash seed");
-        std::vector<Sketch> out;
-        for (const auto& file : files) {
+        constexpr size_t kBatchBases = 1ull << 30, kBatchRecords = 1ull << 22;
+        std::vector<Sketch> out(files.size());
+        Batch b; std::string seq;
+        std::vector<uint32_t> first, len; std::vector<size_t> owner;  // group g of the batch = records [first[g], first[g + 1]) of file owner[g]
+        std::vector<uint64_t> rows, valid, merged;
+        auto flush = [&]() {
+            if (owner.empty()) return;
+            first.push_back((uint32_t)b.n());
+            pool_groups(b, first, kmer, seed, (uint32_t)sketch_size, true, rows, len, valid);
+            for (size_t g = 0; g < owner.size(); ++g) {
+                Sketch& sk = out[owner[g]];
+                const uint64_t* row = rows.data() + g * sketch_size;
+                sk.num_valid_kmers += valid[g];  // [UPSTREAM-RECALL] finch: k-mers pushed to the sketcher
+                if (sk.hashes.empty()) { sk.hashes.assign(row, row + len[g]); continue; }
+                merged.clear();
+                std::set_union(sk.hashes.begin(), sk.hashes.end(), row, row + len[g], std::back_inserter(merged));
+                if (merged.size() > sketch_size) merged.resize(sketch_size);
+                sk.hashes.swap(merged);
+            }
+            b.clear(); first.clear(); owner.clear();
+        };
+        for (size_t fi = 0; fi < files.size(); ++fi) {
+            const auto& file = files[fi];
             FastxReader reader(file);
-            Sketch sk;
+            Sketch& sk = out[fi];
             const auto slash = file.find_last_of('/');
             sk.name = slash == std::string::npos ? file : file.substr(slash + 1);
             sk.kmer_length = kmer; sk.hash_seed = seed;
-            Batch b; std::string seq;
-            std::vector<uint64_t> rows, merged; std::vector<uint32_t> len;
-            auto flush = [&]() {
-                if (b.n() == 0) return;
-                rows.assign(b.n() * sketch_size, 0); len.assign(b.n(), 0);
-                hip_check(skx_sketch_reads(device_, kmer, seed, (uint32_t)sketch_size, b.bases.data(), b.offsets.data(), (uint32_t)b.n(), rows.data(), len.data()), "sketch");
-                for (size_t r = 0; r < b.n(); ++r) {
-                    merged.clear();
-                    std::set_union(sk.hashes.begin(), sk.hashes.end(), rows.begin() + r * sketch_size, rows.begin() + r * sketch_size + len[r], std::back_inserter(merged));
-                    if (merged.size() > sketch_size) merged.resize(sketch_size);
-                    sk.hashes.swap(merged);
-                }
-                b.clear();
-            };
+            if (b.bases.size() >= kBatchBases) flush();
+            owner.push_back(fi); first.push_back((uint32_t)b.n());
             while (reader.next(seq)) {
                 sk.seq_length += seq.size();                       // [UPSTREAM-RECALL] finch: total bases of the records
-                sk.num_valid_kmers += count_valid_kmers(seq, kmer);  // [UPSTREAM-RECALL] finch: k-mers pushed to the sketcher
-                if (b.n() && (b.bases.size() + seq.size() > (1ull << 30) || b.n() * sketch_size > (1ull << 24))) flush();
                 if (seq.size() >= (1ull << 32)) throw SketchyError("a record of " + file + " exceeds 4 Gbases");
+                if (b.n() && (b.bases.size() + seq.size() > kBatchBases || b.n() >= kBatchRecords)) {
+                    flush();
+                    owner.push_back(fi); first.push_back(0);  // the file goes on in the next batch
+                }
                 b.add(seq);
             }
-            flush();
-            out.push_back(std::move(sk));
         }
+        flush();
         write_mash_file(output, out, kmer, (uint32_t)seed);
     }
     // windows of k bases that are all A/C/G/T/U (any case), as needletail's normalize + canonical_kmers see them
-    static uint64_t count_valid_kmers(const std::string& seq, uint32_t k) {
+    static uint64_t count_valid_kmers(const uint8_t* seq, size_t len, uint32_t k) {
         uint64_t n = 0; uint32_t run = 0;
-        for (unsigned char c : seq) {
+        for (size_t i = 0; i < len; ++i) {
+            const unsigned char c = seq[i];
             if (c == ' ' || c == '\t' || c == '\r' || c == '\n') continue;
             const unsigned char u = c & 0xDF;
             run = (u == 'A' || u == 'C' || u == 'G' || u == 'T' || u == 'U') ? run + 1 : 0;
@@ -203,6 +222,39 @@ class Sketchy {
     struct Batch { std::vector<uint8_t> bases; std::vector<uint64_t> offsets{0}; size_t n() const { return offsets.size() - 1; }
                    void add(const std::string& seq) { bases.insert(bases.end(), seq.begin(), seq.end()); offsets.push_back(bases.size()); }
                    void clear() { bases.clear(); offsets.assign(1, 0); } };
+
+    // One pooled bottom-s row per group of the batch's records (group g = records [first[g], first[g + 1])): rows [groups][s]
+    // zero-padded, their lengths and -- want_valid -- the groups' valid k-mer windows.
+    void pool_groups(const Batch& b, const std::vector<uint32_t>& first, uint32_t k, uint64_t seed, uint32_t s, bool want_valid,
+                     std::vector<uint64_t>& rows, std::vector<uint32_t>& len, std::vector<uint64_t>& valid) {
+        const size_t ng = first.size() - 1;
+        rows.assign(ng * (size_t)s, 0); len.assign(ng, 0); valid.assign(ng, 0);
+        if (skx_sketch_groups) {
+            hip_check(skx_sketch_groups(device_, k, seed, s, b.bases.data(), b.offsets.data(), (uint32_t)b.n(), first.data(), (uint32_t)ng,
+                                        rows.data(), len.data(), want_valid ? valid.data() : nullptr), "sketch");
+            return;
+        }
+        // a library without the pooled entry point: one row per record (at most 2^24 row entries per call), merged here
+        const size_t step = std::max<size_t>(1, (1ull << 24) / s);
+        std::vector<uint64_t> sk, pooled, merged; std::vector<uint32_t> sl;
+        for (size_t g = 0; g < ng; ++g) {
+            pooled.clear();
+            for (size_t r0 = first[g]; r0 < first[g + 1]; r0 += step) {
+                const size_t n = std::min<size_t>(step, first[g + 1] - r0);
+                sk.assign(n * (size_t)s, 0); sl.assign(n, 0);
+                hip_check(skx_sketch_reads(device_, k, seed, s, b.bases.data(), b.offsets.data() + r0, (uint32_t)n, sk.data(), sl.data()), "sketch");
+                for (size_t r = 0; r < n; ++r) {
+                    merged.clear();
+                    std::set_union(pooled.begin(), pooled.end(), sk.begin() + r * s, sk.begin() + r * s + sl[r], std::back_inserter(merged));
+                    if (merged.size() > s) merged.resize(s);
+                    pooled.swap(merged);
+                    if (want_valid) valid[g] += count_valid_kmers(b.bases.data() + b.offsets[r0 + r], b.offsets[r0 + r + 1] - b.offsets[r0 + r], k);
+                }
+            }
+            std::copy(pooled.begin(), pooled.end(), rows.begin() + g * (size_t)s);
+            len[g] = (uint32_t)pooled.size();
+        }
+    }
 
     // ---- streaming pipeline
     // one batch travelling parse -> device -> format and back: page-locked (skx_host_alloc) packed bases, offsets (in bases),
@@ -641,21 +693,20 @@ class Sketchy {
         }
     }
 
-    // offline mode: one sketcher over all reads == bottom-s of the union of the per-read bottom-s sketches
+    // offline mode: one sketcher over all reads == bottom-s of the union of the per-read bottom-s sketches.  Every batch is one
+    // group: the device pools its reads (skx_sketch_groups) and ONE row of s hashes comes back per batch, merged here.
     void shared_hashes(FastxReader& reader, const std::vector<Sketch>& sketches, Ref& ref, const Genotypes& geno,
                        const PredictConfig& config, std::ostream& out) {
         Batch b; std::string seq; size_t read = 0;
-        std::vector<uint64_t> pooled, sk, merged; std::vector<uint32_t> len;
+        std::vector<uint64_t> pooled, sk, merged, valid; std::vector<uint32_t> len, first;
         auto flush = [&]() {
             if (b.n() == 0) return;
-            sk.assign(b.n() * (size_t)ref.s, 0); len.assign(b.n(), 0);
-            hip_check(skx_sketch_reads(device_, ref.k, ref.seed, ref.s, b.bases.data(), b.offsets.data(), (uint32_t)b.n(), sk.data(), len.data()), "sketch");
-            for (size_t r = 0; r < b.n(); ++r) {
-                merged.clear();
-                std::set_union(pooled.begin(), pooled.end(), sk.begin() + r * ref.s, sk.begin() + r * ref.s + len[r], std::back_inserter(merged));
-                if (merged.size() > ref.s) merged.resize(ref.s);
-                pooled.swap(merged);
-            }
+            first.assign({0u, (uint32_t)b.n()});
+            pool_groups(b, first, ref.k, ref.seed, ref.s, false, sk, len, valid);
+            merged.clear();
+            std::set_union(pooled.begin(), pooled.end(), sk.begin(), sk.begin() + len[0], std::back_inserter(merged));
+            if (merged.size() > ref.s) merged.resize(ref.s);
+            pooled.swap(merged);
             b.clear();
         };
         while (reader.next(seq)) {

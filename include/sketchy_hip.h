@@ -19,6 +19,9 @@
  *   skx_stream_table[_add] <- read / seed `sum_of_shared_hashes` (:326, :341)
  *   skx_common_hashes      <- Sketchy::_common_hashes (src/sketchy.rs:419-459) for sketch
  *                             collections (the `shared` all-pairs use at :251-261)
+ *   skx_rank_sketches      <- the tail of Sketchy::_shared_hashes (src/sketchy.rs:304-312): shared hashes against every
+ *                             genome, stable sort, first `top` rows -- for many pooled sketches in one call
+ *   skx_predict_groups     <- all of Sketchy::_shared_hashes (src/sketchy.rs:281-315) for many samples: pool, count, rank
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
  *   skx_sketch_groups      <- finch SketchScheme::{process x many, to_vec}: ONE sketcher fed several records -- all reads of an
  *                             offline `predict` (src/sketchy.rs:291-302), all contigs of a genome file in `sketch` (:473-478)
@@ -323,6 +326,24 @@ int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const u
  */
 int skx_common_hashes(const skx_ref *ref, const uint64_t *query, const uint32_t *query_len, uint32_t n_query,
                       uint32_t q_stride, uint32_t *common);
+/* Sketchy::_shared_hashes' tail (src/sketchy.rs:304-312) for many query sketches at once: per query and species the first
+ * top_k genomes of (shared desc, index asc), index local to the species.  Queries laid out as for skx_common_hashes (hashes
+ * >= 0xFFFFFFFFFFFFFFFE in a query behave as they do there).
+ * top_idx / top_shared: host arrays [n_query][n_species][top_k]; common: optional [n_query][n_genomes] (NULL to skip),
+ * the counts the rows were taken from.  top_k: 1 .. min(genomes of the smallest species, SKX_MAX_TOP).
+ * The counts stay on the device (a bit-sliced counter over the pass's bit matrix, then one selection per (query, species) that
+ * reads its row a number of times independent of top_k): n_query x n_species x top_k rows come back.
+ * Errors (all found before any device work): NULL required pointer / top_k out of range SKX_ERR_INVALID, a query row that is
+ * not strictly ascending SKX_ERR_UNSORTED.  n_query == 0: SKX_OK, nothing is touched. */
+int skx_rank_sketches(const skx_ref *ref, const uint64_t *query, const uint32_t *query_len, uint32_t n_query, uint32_t q_stride,
+                      uint32_t top_k, uint32_t *top_idx, uint32_t *top_shared, uint32_t *common);
+/* records -> one pooled sketch per group (as skx_sketch_groups, with the reference's k, seed, s and device) -> rows as above.
+ * top_idx / top_shared: [n_groups][n_species][top_k].  sketches / sketch_len / valid_kmers: optional (NULL to skip), as in
+ * skx_sketch_groups.  Works in chunks of groups: the pooled rows pass through at most 256 MiB of host memory.
+ * n_groups == 0: SKX_OK, nothing is touched. */
+int skx_predict_groups(const skx_ref *ref, const uint8_t *bases, const uint64_t *offsets, uint32_t n_records,
+                       const uint32_t *group_first, uint32_t n_groups, uint32_t top_k,
+                       uint32_t *top_idx, uint32_t *top_shared, uint64_t *sketches, uint32_t *sketch_len, uint64_t *valid_kmers);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------- */
 #define SKX_COMM_ID_BYTES 128

@@ -67,6 +67,8 @@ SYMBOLS = [
     ("skx_sketch_reads", _i, [_i, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     ("skx_sketch_groups", _i, [_i, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     ("skx_common_hashes", _i, [_vp, _vp, _vp, _u32, _u32, _vp]),
+    ("skx_rank_sketches", _i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    ("skx_predict_groups", _i, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("skx_comm_unique_id", _i, [_vp]),
     ("skx_comm_create", _i, [_pp, _i, _i, _i, _vp]),
     ("skx_comm_n_ranks", _i, [_vp, C.POINTER(_i)]),

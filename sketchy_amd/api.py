@@ -143,6 +143,58 @@ class ReferenceSketch:
         _lib.check(_lib.load().skx_common_hashes(self._h, _p(query), _p(query_len), nq, stride, _p(out)))
         return out
 
+    def rank_sketches(self, query, query_len=None, top=1, want_common=False):
+        """Sketchy::_shared_hashes' tail for many query sketches in one call: per query and species the first `top` genomes of
+        (shared desc, index asc), counted and selected on the device.  query: [n_query, stride] uint64 ascending rows.
+        Returns (idx, shared[, common]): [n_query, n_species, top] uint32 each (indices local to the species)
+        [, [n_query, n_genomes] uint32: the counts the rows were taken from]."""
+        query = np.ascontiguousarray(query, np.uint64)
+        if query.ndim != 2:
+            raise ValueError("query must be [n_query, stride]")
+        nq, stride = query.shape
+        query_len = np.full(nq, stride, np.uint32) if query_len is None else np.ascontiguousarray(query_len, np.uint32)
+        if query_len.shape != (nq,):
+            raise ValueError("query_len must hold one length per query row")
+        top = int(top)
+        idx = np.zeros((nq, self.n_species, max(top, 0)), np.uint32)
+        shared = np.zeros_like(idx)
+        common = np.zeros((nq, self.n_genomes), np.uint32) if want_common else None
+        if stride == 0:  # rows without a slot: nq empty queries (the library copies rows of at least one slot)
+            if query_len.any():
+                raise ValueError("query_len exceeds the stride of the query rows")
+            query, stride = np.zeros((max(nq, 1), 1), np.uint64), 1
+        _lib.check(_lib.load().skx_rank_sketches(self._h, _p(query), _p(query_len), nq, stride, top, _p(idx), _p(shared),
+                                                 _p(common) if want_common else None))
+        return (idx, shared, common) if want_common else (idx, shared)
+
+    def predict_groups(self, bases, offsets, group_first, top=1, want_sketches=False, want_valid_kmers=False):
+        """Offline `predict` for many samples in one call: records -> one pooled sketch per group (as sketch_groups, with this
+        reference's k, seed and s) -> the first `top` rows per group and species.  Returns (idx, shared) [n_groups, n_species, top]
+        uint32, then -- want_sketches -- the pooled sketches and their lengths, then -- want_valid_kmers -- the groups' valid
+        k-mer windows."""
+        bases = np.ascontiguousarray(bases, np.uint8)
+        offsets = np.ascontiguousarray(offsets, np.uint64)
+        group_first = np.ascontiguousarray(group_first, np.uint32)
+        if offsets.ndim != 1 or len(offsets) < 1 or group_first.ndim != 1 or len(group_first) < 1:
+            raise ValueError("offsets and group_first are 1-D with at least one entry")
+        n, ng = len(offsets) - 1, len(group_first) - 1
+        top = int(top)
+        idx = np.zeros((ng, self.n_species, max(top, 0)), np.uint32)
+        shared = np.zeros_like(idx)
+        sk = np.zeros((ng, self.s), np.uint64) if want_sketches else None
+        sl = np.zeros(ng, np.uint32) if want_sketches else None
+        vk = np.zeros(ng, np.uint64) if want_valid_kmers else None
+        b = bases if len(bases) else np.zeros(1, np.uint8)
+        _lib.check(_lib.load().skx_predict_groups(self._h, _p(b), _p(offsets), n, _p(group_first), ng, top, _p(idx), _p(shared),
+                                                  _p(sk) if want_sketches else None, _p(sl) if want_sketches else None,
+                                                  _p(vk) if want_valid_kmers else None))
+        out = (idx, shared)
+        if want_sketches:
+            out += (sk, sl)
+        if want_valid_kmers:
+            out += (vk,)
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.load().skx_ref_destroy(self._h)

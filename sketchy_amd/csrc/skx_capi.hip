@@ -948,6 +948,7 @@ struct SubPass {
     u32* d_topk_idx = nullptr;
     u64* d_topk_sum = nullptr;
     u32* d_shared = nullptr;      // [rb-ra][n_genomes] or NULL
+    u32* d_counts = nullptr;      // [rb-ra][n_pad] or NULL: the same counts in padded genome order, from the bit-sliced counter (skx_rank_sketches)
     int side = 0;
     void* slot = nullptr;         // host-fed batches: the staging slot whose rows go back to the host behind the ranking
 };
@@ -2140,7 +2141,7 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
     bool ranked = false, all_forced = false, all_ranked = true;
     for (int i = 0; i < n_sub; ++i) {
         const bool r = st->top_k && subs[i].d_topk_idx && subs[i].d_topk_sum;
-        ranked = ranked || r; all_ranked = all_ranked && r && !subs[i].d_shared;
+        ranked = ranked || r; all_ranked = all_ranked && r && !subs[i].d_shared && !subs[i].d_counts;
     }
     const u32* only_if = nullptr;  // device flag: does any batch of the pass rank on the FULL matrix?  (NULL: yes, unconditionally)
     u32 seq = 0;
@@ -2283,7 +2284,7 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
         (void)hint_env;
         all_forced = !cand_env;
         u32 force_full = all_forced ? 0xFFu : 0u;
-        for (int i = 0; i < n_sub; ++i) if (subs[i].d_shared) force_full |= 1u << i;
+        for (int i = 0; i < n_sub; ++i) if (subs[i].d_shared || subs[i].d_counts) force_full |= 1u << i;
         HIPCHK(hipMemsetAsync(st->d_cbad, 0, 64, hs));
         HIPCHK(hipMemsetAsync(st->d_nqc, 0, skx::pass_counter_bytes(), hs));
         const bool pat_rows = st->use_pat && long_rows && ranked && P > 0 && !all_forced;
@@ -2605,6 +2606,14 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
     }
     if (sb.d_shared)
         skx::launch_shared_debug(ls, d_pair_q + sb.p_off, sub_poff, sub_base, 0, n_reads, d_mq, nq_rows, ref->n_genomes, ref->d_real2pad, sb.d_shared, 0);
+    if (sb.d_counts) {
+        // per-row counts of the FULL matrix: seg_sum with one-row segments.  It skips rank groups without a bit (grp_any), so the
+        // buffer is zeroed first; no chunk sums, no pruning
+        HIPCHK(hipMemsetAsync(sb.d_counts, 0, (size_t)n_reads * n_pad * 4, ls));
+        if (P > 0)
+            skx::launch_seg_sum(ls, d_pair_q + sb.p_off, sub_poff, sub_base, 0, n_reads, 1, d_mq, n_pad, nq_rows, sb.d_counts, d_grp_any, nullptr,
+                                st->d_rowany[b], d_nq_rows, spc);
+    }
     HIPCHK(hipGetLastError());
     SKX_MARK("rank: end sub", si);
     }  // sub-passes
@@ -2631,11 +2640,11 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
 
 static int run_pass(skx_stream* st, u32 ra, u32 rb, u32 p_base, u32 P, u32* d_topk_idx, u64* d_topk_sum,
                     u32* d_shared /* [rb-ra][n_genomes] or NULL */, bool update_table, bool inserted = false, u32 q_rows = 0xFFFFFFFFu,
-                    void* slot = nullptr) {
+                    void* slot = nullptr, u32* d_counts = nullptr /* [rb-ra][n_pad] or NULL */) {
     SubPass sb;
     sb.slot = slot;
     sb.ra = ra; sb.rb = rb; sb.p_off = 0; sb.P = P; sb.p_base = p_base; sb.d_topk_idx = d_topk_idx; sb.d_topk_sum = d_topk_sum;
-    sb.d_shared = d_shared; sb.side = st->side;
+    sb.d_shared = d_shared; sb.d_counts = d_counts; sb.side = st->side;
     sb.d_poff = st->d_poff_pass[st->pslot];  // (inserted passes: the front half's copy; else run_pass_multi fills the slot itself)
     return run_pass_multi(st, &sb, 1, update_table, inserted, q_rows);
 }
@@ -3981,6 +3990,133 @@ SKX_API int skx_common_hashes(const skx_ref* ref, const uint64_t* query, const u
     return rc;
 }
 
+// The front half of skx_common_hashes / skx_rank_sketches: argument checks (nothing has touched the device when they fail)
+static int check_queries(const char* who, const uint64_t* query, const uint32_t* query_len, uint32_t n_query, uint32_t q_stride, u32* max_len) {
+    *max_len = 1;
+    for (u32 i = 0; i < n_query; ++i) {
+        if (query_len[i] > q_stride) return fail(SKX_ERR_INVALID, "%s: query_len[%u] exceeds q_stride", who, i);
+        const uint64_t* row = query + (size_t)i * q_stride;
+        for (u32 j = 1; j < query_len[i]; ++j)
+            if (row[j] <= row[j - 1]) return fail(SKX_ERR_UNSORTED, "%s: query %u not strictly ascending at %u", who, i, j);
+        *max_len = std::max(*max_len, query_len[i]);
+    }
+    return SKX_OK;
+}
+// (the range of top_k that holds for every reference first: it needs no handle)
+static int check_top_range(const char* who, uint32_t top_k) {
+    if (top_k < 1 || top_k > SKX_MAX_TOP) return fail(SKX_ERR_INVALID, "%s: top_k=%u outside 1..SKX_MAX_TOP=%u", who, top_k, SKX_MAX_TOP);
+    return SKX_OK;
+}
+static int check_top(const char* who, const skx_ref* ref, uint32_t top_k) {
+    if (top_k > ref->min_species) return fail(SKX_ERR_INVALID, "%s: top_k=%u exceeds the smallest species' n_genomes=%u", who, top_k, ref->min_species);
+    return SKX_OK;
+}
+static_assert(SKX_MAX_TOP <= skx::kRowTopkMax, "row_topk_kernel orders its rows in one wave");
+
+// max_len: the longest query (skx_rank_sketches' and skx_predict_groups' shared back half; arguments checked by the callers)
+static int rank_sketches_checked(const skx_ref* ref, const uint64_t* query, const uint32_t* query_len, uint32_t n_query, uint32_t q_stride,
+                                 uint32_t top_k, uint32_t* top_idx, uint32_t* top_shared, uint32_t* common, u32 max_len) {
+    skx_stream* st = nullptr;
+    SKXCHK(stream_create_internal(&st, ref, 0, n_query, 1, max_len, max_len, true));  // (whole sketches: every hash is a pair)
+    DevMem m_cnt, m_idx, m_val, m_common;
+    const u32 n_sp = ref->n_species, n_pad = ref->n_pad;
+    int rc = SKX_OK;
+    do {
+        // candidate prefix of every query: hashes <= max_ref (ascending rows)
+        st->h_poff[0] = 0;
+        for (u32 i = 0; i < n_query; ++i) {
+            const uint64_t* row = query + (size_t)i * q_stride;
+            u32 c = ref->any ? (u32)(std::upper_bound(row, row + query_len[i], (uint64_t)ref->max_ref) - row) : 0;
+            st->h_poff[i + 1] = st->h_poff[i] + c;
+        }
+        hipError_t e = use_rows(st);  // (the queries are full-width rows)
+        if (e == hipSuccess) e = hipMemcpy2D(st->d_sk, (size_t)max_len * 8, query, (size_t)q_stride * 8, (size_t)max_len * 8, n_query, hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(st->d_poff, st->h_poff, ((size_t)n_query + 1) * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { rc = fail(SKX_ERR_HIP, "skx_rank_sketches upload: %s", hipGetErrorString(e)); break; }
+        // the padded counts of a pass: [rows][n_pad] u32, at most 256 MB
+        const u32 out_cap = (u32)std::max<u64>(1, (256ull << 20) / ((u64)n_pad * 4));
+        rc = for_each_pass(st, n_query, out_cap, [&](u32 ra, u32 rb, u32 p_base, u32 P) -> int {
+            const u32 rows = rb - ra;
+            HIPCHK(m_cnt.need((size_t)rows * n_pad * 4));
+            HIPCHK(m_idx.need((size_t)rows * n_sp * top_k * 4));
+            HIPCHK(m_val.need((size_t)rows * n_sp * top_k * 4));
+            if (common) HIPCHK(m_common.need((size_t)rows * ref->n_genomes * 4));
+            u32 bound = 0;  // no count of the pass exceeds its longest query
+            for (u32 i = ra; i < rb; ++i) bound = std::max(bound, query_len[i]);
+            if (P == 0) {  // no candidate pairs: all-zero counts, rows 0 .. top_k-1
+                HIPCHK(hipMemsetAsync(m_cnt.p, 0, (size_t)rows * n_pad * 4, st->hs2));
+            } else {
+                SKXCHK(run_pass(st, ra, rb, p_base, P, nullptr, nullptr, nullptr, false, false, 0xFFFFFFFFu, nullptr, m_cnt.as<u32>()));
+                SKXCHK(queue_chains(st, true));  // (the counts are queued on hs2: a pass of one batch ranks on lane 0)
+            }
+            skx::launch_row_topk(st->hs2, m_cnt.as<u32>(), rows, n_pad, ref->species(), top_k, bound, m_idx.as<u32>(), m_val.as<u32>());
+            if (common) skx::launch_unpad_rows(st->hs2, m_cnt.as<u32>(), rows, n_pad, ref->n_genomes, ref->d_real2pad, m_common.as<u32>());
+            HIPCHK(hipGetLastError());
+            const size_t out_at = (size_t)ra * n_sp * top_k, out_n = (size_t)rows * n_sp * top_k * 4;
+            HIPCHK(hipMemcpyAsync(top_idx + out_at, m_idx.p, out_n, hipMemcpyDeviceToHost, st->hs2));
+            HIPCHK(hipMemcpyAsync(top_shared + out_at, m_val.p, out_n, hipMemcpyDeviceToHost, st->hs2));
+            if (common)
+                HIPCHK(hipMemcpyAsync(common + (size_t)ra * ref->n_genomes, m_common.p, (size_t)rows * ref->n_genomes * 4, hipMemcpyDeviceToHost, st->hs2));
+            HIPCHK(hipStreamSynchronize(st->hs2));
+            return SKX_OK;
+        });
+    } while (0);
+    stream_free(st);
+    return rc;
+}
+
+SKX_API int skx_rank_sketches(const skx_ref* ref, const uint64_t* query, const uint32_t* query_len, uint32_t n_query, uint32_t q_stride,
+                              uint32_t top_k, uint32_t* top_idx, uint32_t* top_shared, uint32_t* common) {
+    SKXCHK(check_top_range("skx_rank_sketches", top_k));
+    if (!ref || !query || !query_len || !top_idx || !top_shared) return fail(SKX_ERR_INVALID, "skx_rank_sketches: NULL argument");
+    SKXCHK(check_top("skx_rank_sketches", ref, top_k));
+    if (n_query == 0) return SKX_OK;
+    u32 max_len = 1;
+    SKXCHK(check_queries("skx_rank_sketches", query, query_len, n_query, q_stride, &max_len));
+    return rank_sketches_checked(ref, query, query_len, n_query, q_stride, top_k, top_idx, top_shared, common, max_len);
+}
+
+SKX_API int skx_predict_groups(const skx_ref* ref, const uint8_t* bases, const uint64_t* offsets, uint32_t n_records,
+                               const uint32_t* group_first, uint32_t n_groups, uint32_t top_k, uint32_t* top_idx, uint32_t* top_shared,
+                               uint64_t* sketches, uint32_t* sketch_len, uint64_t* valid_kmers) {
+    SKXCHK(check_top_range("skx_predict_groups", top_k));
+    if (!ref || !offsets || !group_first || !top_idx || !top_shared) return fail(SKX_ERR_INVALID, "skx_predict_groups: NULL argument");
+    SKXCHK(check_top("skx_predict_groups", ref, top_k));
+    for (u32 r = 0; r < n_records; ++r)
+        if (offsets[r + 1] < offsets[r]) return fail(SKX_ERR_INVALID, "skx_predict_groups: offsets not monotonic at record %u", r);
+    if (group_first[0] != 0) return fail(SKX_ERR_INVALID, "skx_predict_groups: group_first[0] must be 0");
+    for (u32 g = 0; g < n_groups; ++g)
+        if (group_first[g + 1] < group_first[g]) return fail(SKX_ERR_INVALID, "skx_predict_groups: group_first decreases at group %u", g);
+    if (group_first[n_groups] != n_records)
+        return fail(SKX_ERR_INVALID, "skx_predict_groups: group_first[n_groups] = %u must be n_records = %u", group_first[n_groups], n_records);
+    if (n_records && offsets[n_records] > offsets[0] && !bases) return fail(SKX_ERR_INVALID, "skx_predict_groups: bases is NULL");
+    if (n_groups == 0) return SKX_OK;
+    // pool, then rank, in chunks of groups whose pooled rows (here on the host between the two halves) stay within kPoolOutBytes
+    const u32 s = ref->s_read, n_sp = ref->n_species;
+    u32 chunk = (u32)std::min<u64>(n_groups, std::max<u64>(1, kPoolOutBytes / ((u64)s * 8)));
+#ifdef SKX_EXPERIMENTS
+    if (const char* e = skx::knob("SKX_PREDICT_GROUPS")) chunk = (u32)std::min<u64>(n_groups, std::max<u64>(1, strtoull(e, nullptr, 10)));  // (tests: chunks at toy size)
+#endif
+    std::vector<u64> rows;
+    std::vector<u32> len, first;
+    if (!sketches) rows.resize((size_t)chunk * s);
+    if (!sketch_len) len.resize(chunk);
+    for (u32 g0 = 0; g0 < n_groups; g0 += chunk) {
+        const u32 ng = std::min(chunk, n_groups - g0), r0 = group_first[g0];
+        first.resize((size_t)ng + 1);
+        for (u32 g = 0; g <= ng; ++g) first[g] = group_first[g0 + g] - r0;
+        u64* sk = sketches ? reinterpret_cast<u64*>(sketches) + (size_t)g0 * s : rows.data();
+        u32* sl = sketch_len ? sketch_len + g0 : len.data();
+        SKXCHK(skx_sketch_groups(ref->device, ref->k, ref->seed, s, bases, offsets + r0, first[ng], first.data(), ng,
+                                 reinterpret_cast<uint64_t*>(sk), sl, valid_kmers ? valid_kmers + g0 : nullptr));
+        u32 max_len = 1;
+        for (u32 g = 0; g < ng; ++g) max_len = std::max(max_len, sl[g]);
+        const size_t out_at = (size_t)g0 * n_sp * top_k;
+        SKXCHK(rank_sketches_checked(ref, reinterpret_cast<const uint64_t*>(sk), sl, ng, s, top_k, top_idx + out_at, top_shared + out_at, nullptr, max_len));
+    }
+    return SKX_OK;
+}
+
 // ------------------------------------------------------------------ RCCL (loaded on first use)
 struct RcclApi {
     void* h = nullptr;
@@ -4107,4 +4243,28 @@ SKX_API void skx_comm_destroy(skx_comm* comm) {
 namespace skx { void rank_debug_counters(unsigned long long* out, bool reset); }
 // experiments build only: counters of rank_seg_top1_kernel (see skx_kernels.hip); out[128]
 SKX_API void skx_debug_rank_counters(unsigned long long* out, int reset) { skx::rank_debug_counters(out, reset != 0); }
+// experiments build only: row_topk_kernel alone on a caller's counts [n_rows][n] (one species of n genomes, padded to whole rank groups
+// here): what skx_rank_sketches cannot reach at test sizes -- bounds of three and four significant bytes.  top_idx / top_val [n_rows][top_k]
+SKX_API int skx_debug_row_topk(int device, const uint32_t* counts, uint32_t n_rows, uint32_t n, uint32_t top_k, uint32_t bound,
+                               uint32_t* top_idx, uint32_t* top_val) {
+    if (!counts || !top_idx || !top_val || n_rows < 1 || n < 1) return fail(SKX_ERR_INVALID, "skx_debug_row_topk: bad argument");
+    if (top_k < 1 || top_k > SKX_MAX_TOP || top_k > n) return fail(SKX_ERR_INVALID, "skx_debug_row_topk: top_k=%u outside 1..min(n, SKX_MAX_TOP)", top_k);
+    SKXCHK(use_device(device));
+    const u32 n_pad = (n + kGroupGenomes - 1) / kGroupGenomes * kGroupGenomes;
+    DevMem m_cnt, m_sp, m_idx, m_val;
+    HIPCHK(m_cnt.need((size_t)n_rows * n_pad * 4));
+    HIPCHK(m_sp.need(2 * 4));
+    HIPCHK(m_idx.need((size_t)n_rows * top_k * 4));
+    HIPCHK(m_val.need((size_t)n_rows * top_k * 4));
+    const u32 sp_host[2] = {0u, n};  // g0, n
+    HIPCHK(hipMemset(m_cnt.p, 0xFF, (size_t)n_rows * n_pad * 4));  // (pad genomes hold the largest value: they must never appear)
+    HIPCHK(hipMemcpy2D(m_cnt.p, (size_t)n_pad * 4, counts, (size_t)n * 4, (size_t)n * 4, n_rows, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(m_sp.p, sp_host, sizeof sp_host, hipMemcpyHostToDevice));
+    const skx::Species sp{m_sp.as<u32>(), m_sp.as<u32>() + 1, nullptr, 1};
+    skx::launch_row_topk(nullptr, m_cnt.as<u32>(), n_rows, n_pad, sp, top_k, bound, m_idx.as<u32>(), m_val.as<u32>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(top_idx, m_idx.p, (size_t)n_rows * top_k * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(top_val, m_val.p, (size_t)n_rows * top_k * 4, hipMemcpyDeviceToHost));
+    return SKX_OK;
+}
 #endif

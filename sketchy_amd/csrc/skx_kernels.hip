@@ -4156,6 +4156,108 @@ __global__ __launch_bounds__(256) void shared_debug_kernel(const u32* __restrict
     }
 }
 
+// row_topk: the first top_k genomes of (count desc, index asc) -- ranks_before on u32 counts -- of one species in one row of
+// padded counts (seg_sum with seg_len = 1: cnt[row][n_pad]).  One workgroup per (row, species) over the species' REAL genomes
+// (sp.n: pad genomes never appear).  The row is read once per significant byte of `bound` (an upper bound of every count: the
+// longest query of the pass) plus once -- whatever top_k:
+//   1. radix select of the top_k-th largest count T, most significant byte first: a 256-bin LDS histogram of the byte among the
+//      counts that share the bytes chosen so far; one wave walks the bins from 255 down;
+//   2. one ordered sweep in tiles of 256 (ballot + prefix over the waves): every count > T is kept (fewer than top_k of them) and
+//      of the counts == T the first top_k - (number above) in ascending index;
+//   3. the top_k kept entries are ordered by counting ranks in one wave.
+// Integer and deterministic; the only atomics are the histogram's, in LDS.
+__global__ __launch_bounds__(256) void row_topk_kernel(const u32* __restrict__ cnt, u32 n_pad, Species sp, u32 top_k, u32 bound,
+                                                       u32* __restrict__ top_idx, u32* __restrict__ top_val) {
+    __shared__ u32 hist[256];
+    __shared__ u32 s_sel[2];      // the bytes chosen so far; entries still wanted among the counts that share them
+    __shared__ u32 wcnt[2][8];    // per tile parity: the four waves' entries above T, then equal to T
+    __shared__ u32 kept_v[kRowTopkMax], kept_i[kRowTopkMax];
+    static_assert(kRowTopkMax == 64, "one wave orders the kept entries");
+    const u32 row = blockIdx.x / sp.n_sp, s_ = blockIdx.x % sp.n_sp;
+    const u32 n = sp.n[s_];
+    const u32* __restrict__ v = cnt + (size_t)row * n_pad + sp.g0[s_];
+    const u32 tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
+    if (top_k == 0 || top_k > kRowTopkMax || top_k > n) return;  // (the entry point has checked; uniform)
+    // ---- 1. the top_k-th largest count
+    u32 prefix = 0, want = top_k;
+    if (tid == 0) { s_sel[0] = 0; s_sel[1] = top_k; }
+    for (int b = bound >> 24 ? 3 : bound >> 16 ? 2 : bound >> 8 ? 1 : 0; b >= 0; --b) {
+        const u32 shift = 8u * (u32)b;
+        const u32 himask = b == 3 ? 0u : ~0u << (shift + 8u);
+        hist[tid] = 0;
+        __syncthreads();
+        for (u32 g = tid; g < n; g += 256u) {
+            const u32 x = v[g];
+            if ((x & himask) == prefix) atomicAdd(&hist[(x >> shift) & 255u], 1u);
+        }
+        __syncthreads();
+        if (wv == 0) {  // lane l: bins 255 - 4l .. 252 - 4l; the bin where the running count from the top reaches `want`
+            u32 h[4], tot = 0;
+#pragma unroll
+            for (u32 i = 0; i < 4u; ++i) { h[i] = hist[255u - 4u * lane - i]; tot += h[i]; }
+            u32 incl = tot;
+#pragma unroll
+            for (u32 d = 1; d < 64u; d <<= 1) {
+                const u32 o = (u32)__shfl_up((int)incl, d, 64);
+                if (lane >= d) incl += o;
+            }
+            const u32 excl = incl - tot;
+            if (excl < want && want <= incl) {  // (exactly one lane: want <= the counts that share the prefix)
+                u32 rem = want - excl, i = 0;
+                while (i < 3u && rem > h[i]) { rem -= h[i]; ++i; }
+                s_sel[0] = prefix | ((255u - 4u * lane - i) << shift);
+                s_sel[1] = rem;
+            }
+        }
+        __syncthreads();
+        prefix = s_sel[0]; want = s_sel[1];
+    }
+    // ---- 2. everything above T, and the first `need` entries equal to it
+    const u32 T = prefix, need = want, n_above = top_k - need;
+    const u64 lt = lanemask_lt();
+    u32 a_base = 0, e_base = 0;
+    for (u32 t0 = 0; t0 < n; t0 += 256u) {
+        const u32 g = t0 + tid, par = (t0 >> 8) & 1u;
+        const u32 x = g < n ? v[g] : 0u;
+        const bool ab = g < n && x > T, eq = g < n && x == T;
+        const u64 ma = __ballot(ab), me = __ballot(eq);
+        if (lane == 0) { wcnt[par][wv] = (u32)__popcll(ma); wcnt[par][4u + wv] = (u32)__popcll(me); }
+        __syncthreads();  // (one barrier per tile: the counters alternate between two sets)
+        u32 a_off = a_base, e_off = e_base;
+#pragma unroll
+        for (u32 w = 0; w < 4u; ++w) {
+            const u32 ca = wcnt[par][w], ce = wcnt[par][4u + w];
+            if (w < wv) { a_off += ca; e_off += ce; }
+            a_base += ca; e_base += ce;
+        }
+        if (ab) {
+            const u32 slot = a_off + (u32)__popcll(ma & lt);
+            if (slot < n_above) { kept_v[slot] = x; kept_i[slot] = g; }
+        }
+        if (eq) {
+            const u32 r = e_off + (u32)__popcll(me & lt);
+            if (r < need) { kept_v[n_above + r] = x; kept_i[n_above + r] = g; }
+        }
+        if (a_base >= n_above && e_base >= need) break;  // (uniform: nothing further can be kept)
+    }
+    __syncthreads();
+    // ---- 3. order the kept entries
+    if (wv == 0 && lane < top_k) {
+        const u32 x = kept_v[lane], g = kept_i[lane];
+        u32 before = 0;
+        for (u32 i = 0; i < top_k; ++i) before += ranks_before(kept_v[i], kept_i[i], x, g) ? 1u : 0u;
+        top_idx[(size_t)blockIdx.x * top_k + before] = g;
+        top_val[(size_t)blockIdx.x * top_k + before] = x;
+    }
+}
+// out[row][g] = cnt[row][real2pad[g]]: the padded counts as the caller sees them (real genomes, species concatenated)
+__global__ __launch_bounds__(256) void unpad_rows_kernel(const u32* __restrict__ cnt, u32 n_pad, u32 n_real, u32 n_rows,
+                                                         const u32* __restrict__ real2pad, u32* __restrict__ out) {
+    const u32 per_row = (n_real + 255u) / 256u;
+    const u32 row = blockIdx.x / per_row, g = (blockIdx.x % per_row) * 256u + threadIdx.x;
+    if (row < n_rows && g < n_real) out[(size_t)row * n_real + g] = cnt[(size_t)row * n_pad + real2pad[g]];
+}
+
 // the table as the caller sees it (real genomes, species concatenated) <-> the padded table of the kernels
 __global__ void add_table_kernel(u64* __restrict__ cum, const u64* __restrict__ add, u32 n_real, const u32* __restrict__ real2pad) {
     const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -5636,6 +5738,14 @@ void launch_shared_debug(hipStream_t st, const u32* pair_q, const u32* poff, u32
     if (n_reads == 0) return;
     hipLaunchKernelGGL(shared_debug_kernel, dim3(n_reads), dim3(256), 0, st, pair_q, poff, p_base, r_begin, mq, n_real, real2pad,
                        shared, out_r0, nq_rows);
+}
+void launch_row_topk(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, const Species& sp, u32 top_k, u32 bound, u32* top_idx, u32* top_val) {
+    if (n_rows == 0) return;
+    hipLaunchKernelGGL(row_topk_kernel, dim3(n_rows * sp.n_sp), dim3(256), 0, st, cnt, n_pad, sp, top_k, bound, top_idx, top_val);
+}
+void launch_unpad_rows(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, u32 n_real, const u32* real2pad, u32* out) {
+    if (n_rows == 0 || n_real == 0) return;
+    hipLaunchKernelGGL(unpad_rows_kernel, dim3(n_rows * cdiv(n_real, 256)), dim3(256), 0, st, cnt, n_pad, n_real, n_rows, real2pad, out);
 }
 void launch_add_table(hipStream_t st, u64* cum, const u64* add, u32 n_real, const u32* real2pad) {
     hipLaunchKernelGGL(add_table_kernel, dim3(cdiv(n_real, 256)), dim3(256), 0, st, cum, add, n_real, real2pad);

@@ -342,6 +342,13 @@ void launch_rank_table(hipStream_t st, const u64* cum, const Species& sp, u32 to
 // n_real real genomes (species concatenated); real2pad[g] = padded index
 void launch_shared_debug(hipStream_t st, const u32* pair_q, const u32* poff, u32 p_base, u32 r_begin, u32 n_reads,
                          const u64* mq, u32 nq_rows, u32 n_real, const u32* real2pad, u32* shared, u32 out_r0);
+// per (row, species) the first top_k of (count desc, index asc) over the species' real genomes of cnt[n_rows][n_pad] (padded counts:
+// launch_seg_sum with seg_len = 1); bound >= every count; top_idx / top_val [n_rows][n_sp][top_k], indices local to the species;
+// 1 <= top_k <= min(kRowTopkMax, smallest species)
+constexpr u32 kRowTopkMax = 64;
+void launch_row_topk(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, const Species& sp, u32 top_k, u32 bound, u32* top_idx, u32* top_val);
+// out[n_rows][n_real] = cnt[row][real2pad[g]]
+void launch_unpad_rows(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, u32 n_real, const u32* real2pad, u32* out);
 void launch_add_table(hipStream_t st, u64* cum, const u64* add, u32 n_real, const u32* real2pad);
 void launch_gather_table(hipStream_t st, const u64* cum, u64* out, u32 n_real, const u32* real2pad);
 

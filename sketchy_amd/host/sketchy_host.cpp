@@ -4,7 +4,7 @@
 //   sketchy::PredictConfig            src/sketchy.rs:43-50
 //   Sketchy::predict                  src/sketchy.rs:66-124   (reference + genotypes + FASTX, header line, mode switch)
 //   Sketchy::_sum_of_shared_hashes    src/sketchy.rs:317-356  (streaming: rows after every read)  -> skx_stream_push
-//   Sketchy::_shared_hashes           src/sketchy.rs:281-315  (offline: one pooled sketch)         -> skx_sketch_groups + skx_common_hashes
+//   Sketchy::_shared_hashes           src/sketchy.rs:281-315  (offline: one pooled sketch per input) -> skx_sketch_groups + skx_rank_sketches
 //   Sketchy::_print_results           src/sketchy.rs:358-402  (rows / consensus)
 //   Sketchy::shared                   src/sketchy.rs:238-279                                       -> skx_common_hashes
 //   Sketchy::info (names only)        src/sketchy.rs:172-208
@@ -45,6 +45,9 @@
 extern "C" int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases, const uint64_t* offsets,
                                  uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
                                  uint32_t* sketch_len, uint64_t* valid_kmers) __attribute__((weak));
+// ... and so is the device-side ranking of many pooled sketches: without it the host takes skx_common_hashes' counts and sorts.
+extern "C" int skx_rank_sketches(const skx_ref* ref, const uint64_t* query, const uint32_t* query_len, uint32_t n_query, uint32_t q_stride,
+                                 uint32_t top_k, uint32_t* top_idx, uint32_t* top_shared, uint32_t* common) __attribute__((weak));
 
 namespace sketchy {
 
@@ -62,8 +65,11 @@ class Sketchy {
   public:
     explicit Sketchy(int device = 0, size_t batch_reads = 16384) : device_(device), batch_(batch_reads) {}
 
-    void predict(const std::optional<std::string>& fastx, const std::string& reference, const std::string& genotypes,
+    // fastx: the inputs (none: stdin).  Offline mode takes several: every path is one sample, its block of rows is what a run on that
+    // file alone prints, in input order (the header once); streaming takes one.
+    void predict(const std::vector<std::string>& fastx, const std::string& reference, const std::string& genotypes,
                  const PredictConfig& config, std::ostream& out) {
+        if (config.stream && fastx.size() > 1) throw SketchyError("--stream takes one input");
         if (config.consensus && config.top % 2 != 1)  // src/sketchy.rs:74-79
             throw SketchyError("--top must be an odd number when using --consensus");
         const auto sketches = read_sketch(reference);
@@ -74,8 +80,8 @@ class Sketchy {
         if (config.top > sketches.size()) throw SketchyError("--top exceeds the number of reference sketches");
         if (config.header) out << "reads\tsketch_id\tshared_hashes\t" << geno.header << "\n";  // :99-101
         Ref ref(sketches, device_);
-        if (config.stream) sum_of_shared_hashes(fastx ? *fastx : std::string("-"), sketches, ref, geno, config, out);
-        else { FastxReader reader(fastx ? *fastx : std::string("-")); shared_hashes(reader, sketches, ref, geno, config, out); }
+        if (config.stream) sum_of_shared_hashes(fastx.empty() ? std::string("-") : fastx[0], sketches, ref, geno, config, out);
+        else shared_hashes(fastx.empty() ? std::vector<std::string>{"-"} : fastx, sketches, ref, geno, config, out);
     }
 
     // `sketchy shared`: every reference x query pair, "ref query common" (src/sketchy.rs:251-276)
@@ -693,37 +699,59 @@ class Sketchy {
         }
     }
 
-    // offline mode: one sketcher over all reads == bottom-s of the union of the per-read bottom-s sketches.  Every batch is one
-    // group: the device pools its reads (skx_sketch_groups) and ONE row of s hashes comes back per batch, merged here.
-    void shared_hashes(FastxReader& reader, const std::vector<Sketch>& sketches, Ref& ref, const Genotypes& geno,
+    // offline mode: one sketcher over all reads of a sample == bottom-s of the union of the per-read bottom-s sketches.  Every batch is
+    // one group: the device pools its reads (skx_sketch_groups) and ONE row of s hashes comes back per batch, merged here.  All samples'
+    // pooled rows are then counted and ranked in ONE call (skx_rank_sketches: `top` rows per sample come back).
+    void shared_hashes(const std::vector<std::string>& paths, const std::vector<Sketch>& sketches, Ref& ref, const Genotypes& geno,
                        const PredictConfig& config, std::ostream& out) {
-        Batch b; std::string seq; size_t read = 0;
-        std::vector<uint64_t> pooled, sk, merged, valid; std::vector<uint32_t> len, first;
-        auto flush = [&]() {
-            if (b.n() == 0) return;
-            first.assign({0u, (uint32_t)b.n()});
-            pool_groups(b, first, ref.k, ref.seed, ref.s, false, sk, len, valid);
-            merged.clear();
-            std::set_union(pooled.begin(), pooled.end(), sk.begin(), sk.begin() + len[0], std::back_inserter(merged));
-            if (merged.size() > ref.s) merged.resize(ref.s);
-            pooled.swap(merged);
-            b.clear();
-        };
-        while (reader.next(seq)) {
-            b.add(seq); ++read;
-            if (b.n() == batch_ || b.bases.size() > (1ull << 29)) flush();
-            if (read == config.limit) break;  // :296-299
+        const size_t n = paths.size(), n_ref = sketches.size();
+        std::vector<std::vector<uint64_t>> pooled(n);
+        std::vector<size_t> reads(n, 0);
+        Batch b; std::string seq;
+        std::vector<uint64_t> sk, merged, valid; std::vector<uint32_t> len, first;
+        for (size_t f = 0; f < n; ++f) {
+            FastxReader reader(paths[f]);
+            auto flush = [&]() {
+                if (b.n() == 0) return;
+                first.assign({0u, (uint32_t)b.n()});
+                pool_groups(b, first, ref.k, ref.seed, ref.s, false, sk, len, valid);
+                merged.clear();
+                std::set_union(pooled[f].begin(), pooled[f].end(), sk.begin(), sk.begin() + len[0], std::back_inserter(merged));
+                if (merged.size() > ref.s) merged.resize(ref.s);
+                pooled[f].swap(merged);
+                b.clear();
+            };
+            while (reader.next(seq)) {
+                b.add(seq); ++reads[f];
+                if (b.n() == batch_ || b.bases.size() > (1ull << 29)) flush();
+                if (reads[f] == config.limit) break;  // :296-299
+            }
+            flush();
         }
-        flush();
-        std::vector<uint32_t> common(sketches.size()), plen{(uint32_t)pooled.size()};
-        if (pooled.empty()) pooled.push_back(0);
-        hip_check(skx_common_hashes(ref.h, pooled.data(), plen.data(), 1, (uint32_t)std::max<size_t>(pooled.size(), 1), common.data()), "common");
-        std::vector<uint32_t> order(sketches.size());
-        for (size_t i = 0; i < order.size(); ++i) order[i] = (uint32_t)i;
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b2) { return common[a] > common[b2]; });  // :310
-        std::vector<uint32_t> idx(order.begin(), order.begin() + config.top); std::vector<uint64_t> sum(config.top);
-        for (size_t j = 0; j < config.top; ++j) sum[j] = common[idx[j]];
-        print_results(sketches, geno, idx.data(), sum.data(), read, config, out);
+        size_t stride = 1;
+        for (const auto& p : pooled) stride = std::max(stride, p.size());
+        std::vector<uint64_t> flat(n * stride, 0);
+        std::vector<uint32_t> plen(n);
+        for (size_t f = 0; f < n; ++f) { std::copy(pooled[f].begin(), pooled[f].end(), flat.begin() + f * stride); plen[f] = (uint32_t)pooled[f].size(); }
+        std::vector<uint32_t> idx(n * config.top), shared(n * config.top);
+        if (skx_rank_sketches && config.top >= 1 && config.top <= SKX_MAX_TOP) {
+            hip_check(skx_rank_sketches(ref.h, flat.data(), plen.data(), (uint32_t)n, (uint32_t)stride, (uint32_t)config.top, idx.data(), shared.data(),
+                                        nullptr), "rank");
+        } else {  // a library without the ranking (or more rows than it ranks): every count comes back, sorted here
+            std::vector<uint32_t> common(n * n_ref), order(n_ref);
+            hip_check(skx_common_hashes(ref.h, flat.data(), plen.data(), (uint32_t)n, (uint32_t)stride, common.data()), "common");
+            for (size_t f = 0; f < n; ++f) {
+                const uint32_t* c = common.data() + f * n_ref;
+                for (size_t i = 0; i < n_ref; ++i) order[i] = (uint32_t)i;
+                std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b2) { return c[a] > c[b2]; });  // :310
+                for (size_t j = 0; j < config.top; ++j) { idx[f * config.top + j] = order[j]; shared[f * config.top + j] = c[order[j]]; }
+            }
+        }
+        std::vector<uint64_t> sum(config.top);
+        for (size_t f = 0; f < n; ++f) {
+            for (size_t j = 0; j < config.top; ++j) sum[j] = shared[f * config.top + j];
+            print_results(sketches, geno, idx.data() + f * config.top, sum.data(), reads[f], config, out);
+        }
     }
 
     // src/sketchy.rs:358-402
@@ -756,7 +784,8 @@ class Sketchy {
 static void usage() {
     std::fprintf(stderr,
                  "sketchy-hip sketch  -o OUT.msh [-i GENOME.fa[.gz] ...] [-s SIZE=1000] [-k K=16] [-e SEED=0]   (paths on stdin without -i)\n"
-                 "sketchy-hip predict -r REF.msh -g GENO.tsv [-i READS.fx[.gz]] [-t TOP] [-l LIMIT] [-s] [-c] [-H] [-b BATCH_READS] [-j THREADS] [--timing] [--pin]\n"
+                 "sketchy-hip predict -r REF.msh -g GENO.tsv [-i READS.fx[.gz] ...] [-t TOP] [-l LIMIT] [-s] [-c] [-H] [-b BATCH_READS] [-j THREADS] [--timing] [--pin]\n"
+                 "                    (without -s: several inputs, one sample each -- the rows of every sample in input order; -l per input; -s: one input)\n"
                  "sketchy-hip shared  -r REF.msh -q QUERY.msh\n"
                  "sketchy-hip info    -i SKETCH.msh [-p]\n"
                  "sketchy-hip check   -r REF.msh -g GENO.tsv\n");
@@ -766,17 +795,19 @@ int main(int argc, char** argv) {
     if (argc < 2) { usage(); return 2; }
     const std::string cmd = argv[1];
     std::map<std::string, std::string> opt; std::map<std::string, bool> flag;
-    std::vector<std::string> inputs;  // `sketch -i` takes several paths (src/cli.rs:27-28: multiple = true)
+    std::vector<std::string> inputs;  // `sketch -i` takes several paths (src/cli.rs:27-28: multiple = true); so does offline `predict -i`
     const std::map<std::string, std::string> longnames = {{"--input", "-i"}, {"--reference", "-r"}, {"--genotypes", "-g"}, {"--top", "-t"}, {"--limit", "-l"},
                                                           {"--stream", "-s"}, {"--consensus", "-c"}, {"--header", "-H"}, {"--query", "-q"}, {"--params", "-p"},
                                                           {"--device", "-d"}, {"--batch", "-b"}, {"--output", "-o"}, {"--sketch-size", "-s"},
                                                           {"--kmer-size", "-k"}, {"--seed", "-e"}, {"--threads", "-j"}, {"--timing", "-T"}, {"--pin", "-P"}};
     const bool is_sketch = cmd == "sketch";  // there -s takes a value (sketch size), elsewhere it is --stream
+    const bool many_inputs = is_sketch || cmd == "predict";
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i];
         if (is_sketch && a == "--stream") { usage(); return 2; }
         if (longnames.count(a)) a = longnames.at(a);
-        if (is_sketch && a == "-i") { while (i + 1 < argc && argv[i + 1][0] != '-') inputs.push_back(argv[++i]); continue; }
+        // (predict: a lone "-" is a path -- stdin)
+        if (many_inputs && a == "-i") { while (i + 1 < argc && (argv[i + 1][0] != '-' || (!is_sketch && !argv[i + 1][1]))) inputs.push_back(argv[++i]); continue; }
         if ((!is_sketch && a == "-s") || a == "-c" || a == "-H" || a == "-p" || a == "-T" || a == "-P") flag[a] = true;
         else if (i + 1 < argc) opt[a] = argv[++i];
         else { usage(); return 2; }
@@ -796,12 +827,16 @@ int main(int argc, char** argv) {
                        opt.count("-k") ? (uint32_t)std::atoi(opt["-k"].c_str()) : 16u, opt.count("-e") ? std::strtoull(opt["-e"].c_str(), nullptr, 10) : 0ull);
         } else if (cmd == "predict") {
             if (!opt.count("-r") || !opt.count("-g")) { usage(); return 2; }
+            if (flag["-s"] && inputs.size() > 1) {
+                std::fprintf(stderr, "Error: predict -s (streaming) takes one input, %zu were given: several inputs are ranked offline (without -s)\n", inputs.size());
+                return 2;
+            }
             sketchy::PredictConfig cfg;
             cfg.top = opt.count("-t") ? (size_t)std::atol(opt["-t"].c_str()) : 1;
             cfg.limit = opt.count("-l") ? (size_t)std::atol(opt["-l"].c_str()) : 0;
             cfg.stream = flag["-s"]; cfg.consensus = flag["-c"]; cfg.header = flag["-H"];
             cfg.threads = opt.count("-j") ? (size_t)std::max(1L, std::atol(opt["-j"].c_str())) : 0; cfg.timing = flag["-T"]; cfg.pin = flag["-P"];
-            app.predict(opt.count("-i") ? std::optional<std::string>(opt["-i"]) : std::nullopt, opt["-r"], opt["-g"], cfg, std::cout);
+            app.predict(inputs, opt["-r"], opt["-g"], cfg, std::cout);
         } else if (cmd == "shared") {
             if (!opt.count("-r") || !opt.count("-q")) { usage(); return 2; }
             app.shared(opt["-r"], opt["-q"], std::cout);

@@ -56,6 +56,7 @@ extern "C" {
 #define SKX_MAX_K 32u             /* k-mer length 1..32 (sketchy default 16, src/cli.rs:39-41) */
 #define SKX_MAX_TOP 64u           /* rows ranked per read (sketchy default 1, src/cli.rs:118-119) */
 #define SKX_MAX_SPECIES 64u       /* reference collections resident together in one skx_ref */
+#define SKX_MAX_FEATURES 64u      /* genotype columns of a reference's genotype table (skx_ref_set_genotypes) */
 
 typedef struct skx_ref skx_ref;
 typedef struct skx_stream skx_stream;
@@ -169,6 +170,23 @@ int skx_ref_patterns(const skx_ref *ref, uint64_t *n_long_lists, uint64_t *n_pat
 int skx_ref_static_dense(const skx_ref *ref, int *is_static, uint64_t *n_hashes);
 /* bytes of reference hashes one scoring pass streams from HBM (8*stride*n_genomes) */
 int skx_ref_pass_bytes(const skx_ref *ref, uint64_t *bytes);
+/*
+ * Genotype table of the reference, for consensus calls on the device (Sketchy::_print_results' consensus branch,
+ * src/sketchy.rs:365-388: every genotype column called by majority over the `top` best genomes).
+ * codes[g][f], uint32, n_features in 1..SKX_MAX_FEATURES; g runs over all genomes of the reference, species one after the other, as
+ * in every genome-indexed array of this header.  Two genomes have the same value in column f iff their codes in column f are equal;
+ * what the codes stand for is the host's business.
+ * CONSENSUS of one ranked row (top_k genome indices of one species) in column f: the code that occurs most often among the top_k
+ * genomes' codes in that column.  TIES GO TO THE SMALLEST CODE.  (The reference takes max_by over a HashMap: which of several tied
+ * values it prints is unspecified.  A host that numbers every column's distinct strings in byte-wise sorted order gets the
+ * lexicographically smallest tied string -- what a std::map walked in order, first maximum kept, gives.)  top_k may be even here.
+ * Consensus output everywhere: codes_out[row][species][n_features] (uint32).
+ * skx_ref_set_genotypes uploads the table (the library keeps its own copy, freed with the reference).  Once per reference, before any
+ * stream of it binds a consensus output: a second call fails with SKX_ERR_INVALID, so no stream ever sees the table change under it.
+ * NULL pointers, n_features of 0 or above SKX_MAX_FEATURES: SKX_ERR_INVALID, before the device is touched.
+ */
+int skx_ref_set_genotypes(skx_ref *ref, uint32_t n_features, const uint32_t *codes); /* [n_genomes][n_features], host */
+int skx_ref_n_features(const skx_ref *ref, uint32_t *n_features);                    /* 0: no table */
 void skx_ref_destroy(skx_ref *ref);
 
 /* ---- streaming predictor ----------------------------------------------------------- */
@@ -260,6 +278,23 @@ int skx_stream_submit(skx_stream *st, const uint8_t *bases, const uint64_t *offs
                       uint32_t *topk_idx, uint64_t *topk_sum, uint64_t *ticket);
 int skx_stream_wait(skx_stream *st, uint64_t ticket);
 int skx_stream_drain(skx_stream *st);
+/*
+ * Consensus codes of a batch (see skx_ref_set_genotypes): binds codes_out [n_reads][n_species][n_features] for the NEXT batch handed
+ * to skx_stream_push, _push_device, _enqueue_device or _submit.  ONE-SHOT: that call consumes the binding whether it succeeds or
+ * fails; a batch call with nothing bound behaves as if this function did not exist and writes no codes anywhere.
+ * codes_out is the kind of memory the entry point's other outputs are: host for skx_stream_push, device for skx_stream_push_device /
+ * skx_stream_enqueue_device, page-locked host for skx_stream_submit; the codes are valid whenever that entry point's rows are.  They
+ * are computed on the device behind the batch's ranking (same queue) from the rows the batch returns, which are the same with and
+ * without a binding.
+ * A bound batch call fails with SKX_ERR_INVALID, before any device work and with the binding consumed, unless: the reference has a
+ * genotype table; the stream has top_k >= 1; for the two _device entry points, d_topk_idx is non-NULL (the stream's own fallback row
+ * buffer is shared by enqueued batches whose rankings run side by side: the vote would race with the next batch's ranking).
+ * skx_stream_push and skx_stream_submit keep a device copy of their rows anyway: with a consensus bound they may be given NULL for
+ * topk_idx and topk_sum, and then only codes travel back.
+ * Device scratch for codes (the stream's own buffer for pushes, one per staging slot for submits) is allocated by the first bound
+ * push / submit: streams that never bind pay nothing.
+ */
+int skx_stream_bind_consensus(skx_stream *st, uint32_t *codes_out);
 /* running sum-of-shared-hashes table, u64[n_genomes] (host) */
 int skx_stream_table(skx_stream *st, uint64_t *cum);
 /* cum[g] += add[g]: resume from a checkpoint, or offset a shard by the totals of earlier shards */
@@ -344,6 +379,12 @@ int skx_rank_sketches(const skx_ref *ref, const uint64_t *query, const uint32_t 
 int skx_predict_groups(const skx_ref *ref, const uint8_t *bases, const uint64_t *offsets, uint32_t n_records,
                        const uint32_t *group_first, uint32_t n_groups, uint32_t top_k,
                        uint32_t *top_idx, uint32_t *top_shared, uint64_t *sketches, uint32_t *sketch_len, uint64_t *valid_kmers);
+/* Consensus codes (skx_ref_set_genotypes: semantics, tie rule) of ranked rows on the host: idx [n_rows][n_species][top_k] as returned
+ * by skx_rank_sketches, skx_predict_groups, skx_stream_rank or any push; codes_out [n_rows][n_species][n_features].  Rows need not
+ * hold distinct genomes.  Works in chunks: at most 64 MiB of rows are on the device at a time.
+ * Errors (all found before any device work): NULL argument, top_k outside 1..SKX_MAX_TOP, no genotype table on the reference, an
+ * index >= its species' genome count: SKX_ERR_INVALID.  n_rows == 0: SKX_OK, nothing is touched. */
+int skx_consensus_rows(const skx_ref *ref, const uint32_t *idx, uint64_t n_rows, uint32_t top_k, uint32_t *codes_out);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------- */
 #define SKX_COMM_ID_BYTES 128

@@ -18,6 +18,7 @@ COMM_ID_BYTES = 128
 MAX_K = 32
 MAX_TOP = 64
 MAX_SPECIES = 64
+MAX_FEATURES = 64
 
 # every symbol include/sketchy_hip.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_size_t
@@ -41,6 +42,8 @@ SYMBOLS = [
     ("skx_ref_n_species", _i, [_vp, C.POINTER(_u32)]),
     ("skx_ref_species_genomes", _i, [_vp, _u32, C.POINTER(_u32)]),
     ("skx_ref_pass_bytes", _i, [_vp, C.POINTER(_u64)]),
+    ("skx_ref_set_genotypes", _i, [_vp, _u32, _vp]),
+    ("skx_ref_n_features", _i, [_vp, C.POINTER(_u32)]),
     ("skx_ref_destroy", None, [_vp]),
     ("skx_stream_create", _i, [_pp, _vp, _u32, _u32, _u64]),
     ("skx_stream_push", _i, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
@@ -54,6 +57,7 @@ SYMBOLS = [
     ("skx_stream_submit", _i, [_vp, _vp, _vp, _u32, _vp, _vp, C.POINTER(_u64)]),
     ("skx_stream_wait", _i, [_vp, _u64]),
     ("skx_stream_drain", _i, [_vp]),
+    ("skx_stream_bind_consensus", _i, [_vp, _vp]),
     ("skx_stream_table", _i, [_vp, _vp]),
     ("skx_stream_table_add", _i, [_vp, _vp]),
     ("skx_stream_reset", _i, [_vp]),
@@ -68,6 +72,7 @@ SYMBOLS = [
     ("skx_sketch_groups", _i, [_i, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
     ("skx_common_hashes", _i, [_vp, _vp, _vp, _u32, _u32, _vp]),
     ("skx_rank_sketches", _i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    ("skx_consensus_rows", _i, [_vp, _vp, _u64, _u32, _vp]),
     ("skx_predict_groups", _i, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("skx_comm_unique_id", _i, [_vp]),
     ("skx_comm_create", _i, [_pp, _i, _i, _i, _vp]),

@@ -66,6 +66,27 @@ def device_mem(device=0):
     return f.value, t.value
 
 
+def encode_genotypes(columns):
+    """Genotype table as integer codes for ReferenceSketch.set_genotypes: columns = one row of strings (or bytes) per genome, all
+    of the same length F.  Returns (codes uint32 [n_genomes, F], values): values[f] lists column f's distinct strings in byte-wise
+    sorted order and the code of a string is its rank there -- so "ties go to the smallest code" is "ties go to the
+    lexicographically smallest string", and values[f][code] turns a consensus code back into its string."""
+    rows = [list(r) for r in columns]
+    n_feat = len(rows[0]) if rows else 0
+    if any(len(r) != n_feat for r in rows):
+        raise ValueError("every genome needs the same number of genotype columns")
+    key = lambda v: v if isinstance(v, bytes) else str(v).encode()
+    codes = np.zeros((len(rows), n_feat), np.uint32)
+    values = []
+    for f in range(n_feat):
+        col = [r[f] for r in rows]
+        distinct = sorted(set(col), key=key)
+        rank = {v: i for i, v in enumerate(distinct)}
+        codes[:, f] = [rank[v] for v in col]
+        values.append(distinct)
+    return codes, values
+
+
 class ReferenceSketch:
     """Reference sketch collection(s) resident in HBM.  hashes: [n_genomes, s] uint64, row g = genome g's ascending
     distinct hashes, first col_len[g] valid -- or a LIST of such matrices, one per species (same s, k, seed): they are
@@ -195,6 +216,36 @@ class ReferenceSketch:
             out += (vk,)
         return out
 
+    def set_genotypes(self, codes):
+        """Make a genotype table part of the resident reference: codes [n_genomes, F] uint32 (species one after the other), equal
+        codes in a column = equal genotype (encode_genotypes).  Once per reference."""
+        codes = np.ascontiguousarray(codes, np.uint32)
+        if codes.ndim != 2 or codes.shape[0] != self.n_genomes:
+            raise ValueError("codes must be [n_genomes, n_features]")
+        _lib.check(_lib.load().skx_ref_set_genotypes(self._h, codes.shape[1], _p(codes)))
+
+    @property
+    def n_features(self) -> int:
+        """columns of the reference's genotype table (0: none was set)"""
+        n = C.c_uint32(0)
+        _lib.check(_lib.load().skx_ref_n_features(self._h, C.byref(n)))
+        return n.value
+
+    def consensus_rows(self, idx) -> np.ndarray:
+        """Consensus code per genotype column of ranked rows: idx [..., top] (one species) or [..., n_species, top] genome indices
+        local to the species, as every ranking entry point returns them -> [..., F] / [..., n_species, F] uint32: the code most of
+        a row's genomes carry, ties to the smallest code."""
+        idx = np.ascontiguousarray(idx, np.uint32)
+        tail = 1 if self.n_species == 1 else 2
+        if idx.ndim < tail or (tail == 2 and idx.shape[-2] != self.n_species):
+            raise ValueError("idx must be [..., top] for one species and [..., n_species, top] for several")
+        top = idx.shape[-1]
+        lead = idx.shape[: idx.ndim - tail]
+        n_rows = int(np.prod(lead, dtype=np.int64))
+        out = np.zeros(lead + idx.shape[idx.ndim - tail:-1] + (self.n_features,), np.uint32)
+        _lib.check(_lib.load().skx_consensus_rows(self._h, _p(idx), n_rows, top, _p(out)))
+        return out
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.load().skx_ref_destroy(self._h)
@@ -219,10 +270,15 @@ class SumOfSharedHashes:
         _lib.check(L.skx_stream_create(C.byref(h), ref._h, self.top, self.max_batch_reads, self.max_batch_bases))
         self._h = h
 
-    def push(self, bases, offsets, want_shared=False, want_sketches=False):
-        """Consume a packed batch; returns dict(topk_idx, topk_sum[, shared, sketches, sketch_len]).  Rows are
+    def bind_consensus(self, codes_out):
+        """Bind a consensus output (pointer / address; [n_reads, n_species, F] uint32) for the NEXT batch call, which consumes it."""
+        _lib.check(_lib.load().skx_stream_bind_consensus(self._h, codes_out))
+
+    def push(self, bases, offsets, want_shared=False, want_sketches=False, want_consensus=False):
+        """Consume a packed batch; returns dict(topk_idx, topk_sum[, shared, sketches, sketch_len, consensus]).  Rows are
         [n_reads, top] for a single reference and [n_reads, n_species, top] (genome indices local to the species)
-        for a multi-species one; shared / table() hold the species one after the other."""
+        for a multi-species one; shared / table() hold the species one after the other.  want_consensus: the consensus codes of
+        every read's rows, [n_reads, F] / [n_reads, n_species, F] (the reference needs a genotype table)."""
         L = _lib.load()
         bases = np.ascontiguousarray(bases, np.uint8)
         offsets = np.ascontiguousarray(offsets, np.uint64)
@@ -235,16 +291,27 @@ class SumOfSharedHashes:
         sk = np.zeros((n, self.ref.s), np.uint64) if want_sketches else None
         sl = np.zeros(n, np.uint32) if want_sketches else None
         b = bases if len(bases) else np.zeros(1, np.uint8)
+        cons = None
+        if want_consensus:
+            cons = np.zeros(shape[:-1] + (self.ref.n_features,), np.uint32)
+            self.bind_consensus(_p(cons))
         _lib.check(L.skx_stream_push(self._h, _p(b), _p(offsets), n, _p(ti), _p(ts), _p(sh), _p(sk), _p(sl)))
         out.update(topk_idx=ti, topk_sum=ts, shared=sh, sketches=sk, sketch_len=sl)
+        if want_consensus:
+            out["consensus"] = cons
         return out
 
-    def push_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None):
+    def push_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None):
+        """consensus: device pointer for the batch's consensus codes, bound right before the call (needs d_topk_idx)"""
+        if consensus is not None:
+            self.bind_consensus(consensus)
         _lib.check(_lib.load().skx_stream_push_device(self._h, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum))
 
-    def enqueue_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None):
+    def enqueue_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None):
         """push_device with the host wait of batch i overlapped by the sketch of batch i + 1: the passes (and any
         error) of a batch are queued by the NEXT enqueue / flush / sync.  Same rows, same table."""
+        if consensus is not None:
+            self.bind_consensus(consensus)
         _lib.check(_lib.load().skx_stream_enqueue_device(self._h, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum))
 
     def flush(self):
@@ -257,9 +324,12 @@ class SumOfSharedHashes:
     def sync(self):
         _lib.check(_lib.load().skx_stream_sync(self._h))
 
-    def submit(self, h_bases, h_offsets, n_reads, h_topk_idx=None, h_topk_sum=None) -> int:
+    def submit(self, h_bases, h_offsets, n_reads, h_topk_idx=None, h_topk_sum=None, consensus=None) -> int:
         """Queue a batch held in page-locked host memory (HostBuffer pointers / addresses); returns its ticket.  The
-        copy overlaps the previous batch's kernels; rows are valid after wait(ticket) or drain()."""
+        copy overlaps the previous batch's kernels; rows are valid after wait(ticket) or drain().  consensus: page-locked
+        pointer for the batch's consensus codes, bound right before the call; the row pointers may then be None."""
+        if consensus is not None:
+            self.bind_consensus(consensus)
         t = C.c_uint64(0)
         _lib.check(_lib.load().skx_stream_submit(self._h, h_bases, h_offsets, n_reads, h_topk_idx, h_topk_sum, C.byref(t)))
         return t.value
@@ -295,6 +365,11 @@ class SumOfSharedHashes:
         idx, sm = np.zeros(shape, np.uint32), np.zeros(shape, np.uint64)
         _lib.check(_lib.load().skx_stream_rank(self._h, top, _p(idx), _p(sm)))
         return idx, sm
+
+    def consensus(self, top=None) -> np.ndarray:
+        """Consensus codes of the CURRENT table: rank(top) followed by the reference's consensus_rows -> [F] / [n_species, F]."""
+        idx, _ = self.rank(top)
+        return self.ref.consensus_rows(idx)
 
     def stats(self):
         """Counters of the stream (skx_stream_stats): pairs / passes of the last push, dictionary size, ..."""

@@ -298,6 +298,10 @@ struct skx_ref {
     u32* d_segw = nullptr;    // [2 n_species] the words of M that hold them
     u32 sd_tail0 = 0;         // first row of the lifted hashes (sorted tail)
     u64 n_forced_rare = 0;    // hashes held by more genomes than rare_hash_genomes that got a list anyway: they occur in several species
+    // genotype table (skx_ref_set_genotypes): [n_pad][n_features] codes in PADDED genome order, so that d_sp_g0[species] + a row's
+    // species-local index names a genome's row (the padding rows are zero and never asked for)
+    u32* d_codes = nullptr;
+    u32 n_features = 0;
     skx::RareIndex rare_index() const {
         skx::RareIndex ri{d_kt_key, d_kt_off, d_kt_cnt, d_post, kt_mask, d_mlong, d_lid, d_lslot, n_pad / 64, d_mlongT, n_lw};
         ri.prec = d_prec; ri.pat_rep = d_pat_rep; ri.pm = d_pm; ri.d_npat = d_npat; ri.n_pat = n_pat;
@@ -318,7 +322,7 @@ static void ref_free(skx_ref* r) {
     (void)hipFree(r->d_mlong); (void)hipFree(r->d_mlongT); (void)hipFree(r->d_lid); (void)hipFree(r->d_lslot);
     (void)hipFree(r->d_prec); (void)hipFree(r->d_pat_rep); (void)hipFree(r->d_npat); (void)hipFree(r->d_pm);
     (void)hipFree(r->d_qs); (void)hipFree(r->d_nsd); (void)hipFree(r->d_win_s);
-    (void)hipFree(r->d_srow); (void)hipFree(r->d_seg); (void)hipFree(r->d_segw);
+    (void)hipFree(r->d_srow); (void)hipFree(r->d_seg); (void)hipFree(r->d_segw); (void)hipFree(r->d_codes);
     delete r;
 }
 
@@ -880,6 +884,31 @@ SKX_API int skx_ref_pass_bytes(const skx_ref* ref, uint64_t* bytes) {
     *bytes = 8ull * ref->s * ref->n_genomes;
     return SKX_OK;
 }
+
+SKX_API int skx_ref_set_genotypes(skx_ref* ref, uint32_t n_features, const uint32_t* codes) {
+    if (!ref || !codes) return fail(SKX_ERR_INVALID, "skx_ref_set_genotypes: NULL argument");
+    if (n_features < 1 || n_features > SKX_MAX_FEATURES)
+        return fail(SKX_ERR_INVALID, "skx_ref_set_genotypes: n_features=%u outside 1..%u", n_features, SKX_MAX_FEATURES);
+    if (ref->d_codes) return fail(SKX_ERR_INVALID, "skx_ref_set_genotypes: the reference already has a genotype table");
+    SKXCHK(use_device(ref->device));
+    // genome g of the caller's order -> its padded row
+    std::vector<u32> padded((size_t)ref->n_pad * n_features, 0u);
+    for (u32 sp = 0; sp < ref->n_species; ++sp)
+        memcpy(padded.data() + (size_t)ref->sp_g0[sp] * n_features, codes + (size_t)ref->sp_real0[sp] * n_features,
+               (size_t)ref->sp_n[sp] * n_features * 4);
+    u32* d = nullptr;
+    HIPCHK(hipMalloc(&d, padded.size() * 4));
+    const hipError_t e = hipMemcpy(d, padded.data(), padded.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(SKX_ERR_HIP, "skx_ref_set_genotypes: %s", hipGetErrorString(e)); }
+    ref->d_codes = d;
+    ref->n_features = n_features;
+    return SKX_OK;
+}
+SKX_API int skx_ref_n_features(const skx_ref* ref, uint32_t* n_features) {
+    if (!ref || !n_features) return fail(SKX_ERR_INVALID, "NULL argument");
+    *n_features = ref->n_features;
+    return SKX_OK;
+}
 SKX_API void skx_ref_destroy(skx_ref* ref) { ref_free(ref); }
 
 // ------------------------------------------------------------------ stream
@@ -915,6 +944,7 @@ struct PendingBatch {
     u64* h_sketches = nullptr;
     u32* h_sketch_len = nullptr;
     void* slot = nullptr;      // skx_stream::Staged of a host-fed batch: its rows travel to the host behind the ranking
+    u32* d_cons = nullptr;     // [n_reads][n_species][n_features] consensus codes of its rows (skx_stream_bind_consensus) or NULL
 };
 
 // The HIP streams of the pipeline, ONE set per device shared by every skx_stream on it.  Measured (tools/diag_second_stream.py,
@@ -951,6 +981,7 @@ struct SubPass {
     u32* d_counts = nullptr;      // [rb-ra][n_pad] or NULL: the same counts in padded genome order, from the bit-sliced counter (skx_rank_sketches)
     int side = 0;
     void* slot = nullptr;         // host-fed batches: the staging slot whose rows go back to the host behind the ranking
+    u32* d_cons = nullptr;        // consensus codes of the BATCH's rows (row 0 = the batch's first read) or NULL
 };
 static const int kSides = kGroupMax + 1;  // copies of the per-batch sketch outputs: the enqueued batches waiting for their shared pass + the one being sketched
                                           // (a stream uses stream_coalesce + 1 of them, allocated at first use)
@@ -1168,6 +1199,10 @@ struct skx_stream {
     u64* d_cum = nullptr;        // running table (current)
     u32* d_topk_idx = nullptr;
     u64* d_topk_sum = nullptr;
+    // consensus codes (skx_stream_bind_consensus): the output bound for the next batch call, and the device buffer a bound
+    // skx_stream_push writes them to ([max_reads][n_species][n_features], allocated by the first such push)
+    u32* bound_cons = nullptr;
+    u32* d_cons = nullptr;
     u64* d_tab_tmp = nullptr;   // [n_genomes] staging of skx_stream_table / skx_stream_table_add
     u32* d_rank_idx = nullptr;  // [n_species][top] outputs of skx_stream_rank
     u64* d_rank_sum = nullptr;
@@ -1212,6 +1247,8 @@ struct skx_stream {
         u64 n_bases = 0, ticket = 0;
         u32* out_idx = nullptr;
         u64* out_sum = nullptr;
+        u32* out_cons = nullptr;    // consensus codes of the batch (page-locked host) or NULL; d_cons: the slot's device copy, allocated
+        u32* d_cons = nullptr;      // for every slot by the first bound submit
         u32* d_rows_idx = nullptr;  // the slot's own device rows (batches may share a pass: each needs its rows until they are copied out)
         u64* d_rows_sum = nullptr;
         uint8_t* d_bases = nullptr;
@@ -1249,7 +1286,7 @@ static void stream_free(skx_stream* st) {
     void* ptrs[] = {st->d_bases, st->d_offsets, st->d_pair_h[0], st->d_pair_h[1],
                     st->d_q[0], st->d_q[1], st->d_pair_r[0], st->d_pair_r[1], st->d_pair_q[0], st->d_pair_q[1],
                     st->d_poff_pass[0], st->d_poff_pass[1], st->d_poff_pass[2], st->d_pair_r[2], st->d_nq[0], st->d_nq[1], st->d_win[0], st->d_win[1], st->d_m, st->d_mint, st->d_mq[0], st->d_mq[1],
-                    st->d_topk_idx, st->d_topk_sum, st->d_tab_tmp, st->d_rank_idx, st->d_rank_sum, st->d_bsum, st->d_grp_any[0],
+                    st->d_topk_idx, st->d_topk_sum, st->d_cons, st->d_tab_tmp, st->d_rank_idx, st->d_rank_sum, st->d_bsum, st->d_grp_any[0],
                     st->d_grp_any[1], st->d_hbuf, st->d_wb[0], st->d_wb[1], st->d_rowany[0], st->d_rowany[1], st->d_mqext,
                     st->d_qd, st->d_qrow, st->d_sslot, st->d_qinfo, st->d_qloc, st->d_cls_bsum, st->d_nd_hs,
                     st->d_rowcnt, st->d_gain, st->d_gain_s, st->d_candslot, st->d_candmask, st->d_lrow, st->d_nlrow, st->d_gain_l, st->d_cbase, st->d_cwl, st->d_ncwl, st->d_cw, st->d_cbad, st->d_nqc, st->d_spc_g0, st->d_spc_grp, st->d_inb, st->d_hit, st->d_hist, st->d_nprow, st->d_pcw, st->d_ms[0], st->d_ms[1], st->d_mdirty_s};
@@ -1279,7 +1316,7 @@ static void stream_free(skx_stream* st) {
     (void)hipFree(st->d_slot_off); (void)hipFree(st->d_bcount); (void)hipFree(st->d_bbase);
     (void)hipFree(st->d_btot);
     for (auto& sl : st->slot) {
-        (void)hipFree(sl.d_bases); (void)hipFree(sl.d_offsets); (void)hipFree(sl.d_rows_idx); (void)hipFree(sl.d_rows_sum);
+        (void)hipFree(sl.d_bases); (void)hipFree(sl.d_offsets); (void)hipFree(sl.d_rows_idx); (void)hipFree(sl.d_rows_sum); (void)hipFree(sl.d_cons);
         if (sl.h_offsets) (void)hipHostFree(sl.h_offsets);
         if (sl.ev_copy) (void)hipEventDestroy(sl.ev_copy);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
@@ -2603,6 +2640,9 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
         if (compact)  // candidate slots -> genome indices (local to the species)
             skx::launch_cand_rows_back(ls, d_topk_idx + (size_t)out_r0 * n_sp * st->top_k, n_reads, n_sp, st->top_k,
                                        ps.cand + (size_t)si * st->n_pad_c, skx::kCandCap, ref->d_sp_g0);
+        if (sb.d_cons)  // the vote over the rows this sub-pass has just finished, behind the last kernel that writes them
+            skx::launch_consensus_rows(ls, d_topk_idx, out_r0, n_reads, n_sp, st->top_k, ref->d_sp_g0, ref->d_codes, ref->n_features,
+                                       sb.d_cons, n_pad);
     }
     if (sb.d_shared)
         skx::launch_shared_debug(ls, d_pair_q + sb.p_off, sub_poff, sub_base, 0, n_reads, d_mq, nq_rows, ref->n_genomes, ref->d_real2pad, sb.d_shared, 0);
@@ -2640,9 +2680,9 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
 
 static int run_pass(skx_stream* st, u32 ra, u32 rb, u32 p_base, u32 P, u32* d_topk_idx, u64* d_topk_sum,
                     u32* d_shared /* [rb-ra][n_genomes] or NULL */, bool update_table, bool inserted = false, u32 q_rows = 0xFFFFFFFFu,
-                    void* slot = nullptr, u32* d_counts = nullptr /* [rb-ra][n_pad] or NULL */) {
+                    void* slot = nullptr, u32* d_counts = nullptr /* [rb-ra][n_pad] or NULL */, u32* d_cons = nullptr) {
     SubPass sb;
-    sb.slot = slot;
+    sb.slot = slot; sb.d_cons = d_cons;
     sb.ra = ra; sb.rb = rb; sb.p_off = 0; sb.P = P; sb.p_base = p_base; sb.d_topk_idx = d_topk_idx; sb.d_topk_sum = d_topk_sum;
     sb.d_shared = d_shared; sb.d_counts = d_counts; sb.side = st->side;
     sb.d_poff = st->d_poff_pass[st->pslot];  // (inserted passes: the front half's copy; else run_pass_multi fills the slot itself)
@@ -3036,7 +3076,7 @@ static int batch_back(skx_stream* st, PendingBatch& pb, PendingBatch* younger) {
             HIPCHK(hipMalloc(&d_shared, (size_t)(rb - ra) * ref->n_genomes * 4));
         }
         SKXCHK(run_pass(st, ra, rb, p_base, P, pb.d_topk_idx, pb.d_topk_sum, d_shared, true, inserted, inserted ? q_rows : 0xFFFFFFFFu,
-                        rb == n_reads ? pb.slot : nullptr));
+                        rb == n_reads ? pb.slot : nullptr, nullptr, pb.d_cons));
         inserted = false;
         st->last_passes += 1;
         if (pb.h_shared) {
@@ -3143,7 +3183,7 @@ static int batch_back_group(skx_stream* st, PendingBatch* g, int n, PendingBatch
         subs[i].d_topk_idx = g[i].d_topk_idx; subs[i].d_topk_sum = g[i].d_topk_sum;
         subs[i].p_off = p_off; subs[i].P = P[i];
         subs[i].d_poff = st->d_poff_pass[g[0].spec_slot] + (size_t)i * ((size_t)st->rpass + 2);
-        subs[i].slot = g[i].slot;
+        subs[i].slot = g[i].slot; subs[i].d_cons = g[i].d_cons;
         p_off += P[i];
     }
     st->last_pairs = pairs; st->last_passes = 1; st->shared_passes += 1;
@@ -3188,13 +3228,13 @@ static int flush_pending(skx_stream* st) {
 // sketch + score + rank a batch already resident on the device, both halves (synchronous entry points).
 // h_shared / h_sketches / h_sketch_len: optional HOST outputs (parity/debug).
 static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_offsets, u32 n_reads, u64 n_bases, u32* d_topk_idx,
-                         u64* d_topk_sum, u32* h_shared, u64* h_sketches, u32* h_sketch_len) {
+                         u64* d_topk_sum, u32* h_shared, u64* h_sketches, u32* h_sketch_len, u32* d_cons = nullptr) {
     if (n_reads == 0) return SKX_OK;
     SKXCHK(flush_pending(st));
     PendingBatch pb;
     pb.d_bases = d_bases; pb.d_offsets = d_offsets; pb.n_reads = n_reads; pb.n_bases = n_bases;
     pb.d_topk_idx = d_topk_idx; pb.d_topk_sum = d_topk_sum;
-    pb.h_shared = h_shared; pb.h_sketches = h_sketches; pb.h_sketch_len = h_sketch_len;
+    pb.h_shared = h_shared; pb.h_sketches = h_sketches; pb.h_sketch_len = h_sketch_len; pb.d_cons = d_cons;
     SKXCHK(batch_front(st, pb));
     st->tail_pass = true;  // (a synchronous push: the batch's passes have the chip to themselves)
     const int rc = batch_back(st, pb, nullptr);
@@ -3206,8 +3246,9 @@ static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_of
 // next group runs the shared back half of the one before it, behind its own front half.  Errors of a batch surface here up to
 // stream_coalesce calls late (or in the flush); the batches enqueued after it up to that call are dropped too.
 static int enqueue_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_offsets, u32 n_reads, u64 n_bases, u32* d_topk_idx,
-                         u64* d_topk_sum, void* slot) {
+                         u64* d_topk_sum, void* slot, u32* d_cons) {
     PendingBatch nw;
+    nw.d_cons = d_cons;
     nw.d_bases = d_bases; nw.d_offsets = d_offsets; nw.n_reads = n_reads; nw.n_bases = n_bases;
     nw.d_topk_idx = d_topk_idx; nw.d_topk_sum = d_topk_sum; nw.slot = slot;
     nw.pairable = st->coalesce >= 2;
@@ -3242,10 +3283,36 @@ static int enqueue_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_of
     return SKX_OK;
 }
 
+// ---- consensus codes of a batch (skx_stream_bind_consensus)
+// every batch entry point begins by taking the binding: it is gone whatever becomes of the call
+static u32* take_consensus(skx_stream* st) {
+    u32* c = st->bound_cons;
+    st->bound_cons = nullptr;
+    return c;
+}
+// what a bound batch call needs (nothing has touched the device when it fails); device_rows: the caller's device row array of the
+// two _device entry points (a stream's own fallback rows are shared between the chains of enqueued batches)
+static int check_consensus(const char* who, const skx_stream* st, bool device_entry, const void* device_rows) {
+    if (!st->ref->d_codes) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but the reference has no genotype table", who);
+    if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but the stream was created with top_k=0", who);
+    if (device_entry && !device_rows) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but d_topk_idx is NULL", who);
+    return SKX_OK;
+}
+static size_t consensus_bytes(const skx_stream* st, u32 n_reads) { return (size_t)n_reads * st->ref->n_species * st->ref->n_features * 4; }
+
+SKX_API int skx_stream_bind_consensus(skx_stream* st, uint32_t* codes_out) {
+    if (!st || !codes_out) return fail(SKX_ERR_INVALID, "skx_stream_bind_consensus: NULL argument");
+    st->bound_cons = codes_out;
+    return SKX_OK;
+}
+
 SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads,
                             uint32_t* topk_idx, uint64_t* topk_sum, uint32_t* per_read_shared, uint64_t* sketches,
                             uint32_t* sketch_len) {
-    if (!st || !offsets) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st) return fail(SKX_ERR_INVALID, "NULL argument");
+    u32* const cons = take_consensus(st);
+    if (!offsets) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (cons) SKXCHK(check_consensus("skx_stream_push", st, false, nullptr));
     if (n_reads == 0) return SKX_OK;
     if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
     for (u32 r = 0; r < n_reads; ++r)
@@ -3256,6 +3323,7 @@ SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t
     if (n_bases && !bases) return fail(SKX_ERR_INVALID, "bases is NULL");
     if ((topk_idx || topk_sum) && st->top_k == 0) return fail(SKX_ERR_INVALID, "stream was created with top_k=0");
     SKXCHK(use_device(st->device));
+    if (cons && !st->d_cons) HIPCHK(hipMalloc(&st->d_cons, consensus_bytes(st, st->max_reads)));
     SKXCHK(flush_pending(st));
     hipStream_t hs = st->hs0;
     // rebase offsets to 0 on the way in (packed input: to the first byte that holds a base of the batch)
@@ -3265,12 +3333,13 @@ SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t
     HIPCHK(hipMemcpyAsync(st->d_offsets, st->h_offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, hs));
     if (n_bases) HIPCHK(hipMemcpyAsync(st->d_bases, bases + byte0, n_bytes, hipMemcpyHostToDevice, hs));
     SKXCHK(process_batch(st, st->d_bases, st->d_offsets, n_reads, n_bases, st->d_topk_idx, st->d_topk_sum,
-                         per_read_shared, reinterpret_cast<u64*>(sketches), sketch_len));
+                         per_read_shared, reinterpret_cast<u64*>(sketches), sketch_len, cons ? st->d_cons : nullptr));
     SKXCHK(queue_chains(st, true));    // the ranking of the batch's last pass (waits for its candidates)
     HIPCHK(hipStreamSynchronize(hs));  // sketch copies (first stream)
     const size_t rows = (size_t)n_reads * st->ref->n_species * st->top_k;
     if (topk_idx) HIPCHK(hipMemcpyAsync(topk_idx, st->d_topk_idx, rows * 4, hipMemcpyDeviceToHost, st->hs2));
     if (topk_sum) HIPCHK(hipMemcpyAsync(topk_sum, st->d_topk_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
+    if (cons) HIPCHK(hipMemcpyAsync(cons, st->d_cons, consensus_bytes(st, n_reads), hipMemcpyDeviceToHost, st->hs2));
     HIPCHK(hipStreamSynchronize(st->hs2));  // the rows are written by the back half
     if (st->profiling) collect_spans(st);
     return SKX_OK;
@@ -3288,21 +3357,25 @@ static int check_device_batch(skx_stream* st, const uint8_t* d_bases, const uint
 }
 SKX_API int skx_stream_push_device(skx_stream* st, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
                                    uint64_t n_bases, uint32_t* d_topk_idx, uint64_t* d_topk_sum) {
+    u32* const cons = st ? take_consensus(st) : nullptr;
     SKXCHK(check_device_batch(st, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum));
+    if (cons) SKXCHK(check_consensus("skx_stream_push_device", st, true, d_topk_idx));
     SKXCHK(use_device(st->device));
     if (n_reads == 0) return flush_pending(st);
     u32* ti = d_topk_idx ? d_topk_idx : st->d_topk_idx;
     u64* ts = d_topk_sum ? reinterpret_cast<u64*>(d_topk_sum) : st->d_topk_sum;
-    return process_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, nullptr, nullptr);
+    return process_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, nullptr, nullptr, cons);
 }
 SKX_API int skx_stream_enqueue_device(skx_stream* st, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
                                       uint64_t n_bases, uint32_t* d_topk_idx, uint64_t* d_topk_sum) {
+    u32* const cons = st ? take_consensus(st) : nullptr;
     SKXCHK(check_device_batch(st, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum));
+    if (cons) SKXCHK(check_consensus("skx_stream_enqueue_device", st, true, d_topk_idx));
     if (n_reads == 0) return SKX_OK;
     SKXCHK(use_device(st->device));
     u32* ti = d_topk_idx ? d_topk_idx : st->d_topk_idx;
     u64* ts = d_topk_sum ? reinterpret_cast<u64*>(d_topk_sum) : st->d_topk_sum;
-    return enqueue_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr);
+    return enqueue_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, cons);
 }
 SKX_API int skx_stream_flush(skx_stream* st) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
@@ -3318,6 +3391,7 @@ static int staged_rows(skx_stream* st, void* slot) {
     const size_t rows = (size_t)sl.n_reads * st->ref->n_species * st->top_k;
     if (sl.out_idx) HIPCHK(hipMemcpyAsync(sl.out_idx, sl.d_rows_idx, rows * 4, hipMemcpyDeviceToHost, st->hs2));
     if (sl.out_sum) HIPCHK(hipMemcpyAsync(sl.out_sum, sl.d_rows_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
+    if (sl.out_cons) HIPCHK(hipMemcpyAsync(sl.out_cons, sl.d_cons, consensus_bytes(st, sl.n_reads), hipMemcpyDeviceToHost, st->hs2));
     HIPCHK(hipEventRecord(sl.ev_done, st->hs2));
     sl.in_flight = true;
     return SKX_OK;
@@ -3330,7 +3404,7 @@ static int staged_process(skx_stream* st, skx_stream::Staged& sl) {
     if (!sl.pending) return SKX_OK;
     sl.pending = false;
     HIPCHK(hipStreamWaitEvent(st->hs0, sl.ev_copy, 0));  // the batch must have landed before the sketcher reads it
-    return enqueue_batch(st, sl.d_bases, sl.d_offsets, sl.n_reads, sl.n_bases, sl.d_rows_idx, sl.d_rows_sum, &sl);
+    return enqueue_batch(st, sl.d_bases, sl.d_offsets, sl.n_reads, sl.n_bases, sl.d_rows_idx, sl.d_rows_sum, &sl, sl.out_cons ? sl.d_cons : nullptr);
 }
 // ... until its rows are on the host
 static int staged_finish(skx_stream* st, skx_stream::Staged& sl) {
@@ -3348,7 +3422,10 @@ static int staged_finish(skx_stream* st, skx_stream::Staged& sl) {
 }
 SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads,
                               uint32_t* topk_idx, uint64_t* topk_sum, uint64_t* ticket) {
-    if (!st || !offsets) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st) return fail(SKX_ERR_INVALID, "NULL argument");
+    u32* const cons = take_consensus(st);
+    if (!offsets) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (cons) SKXCHK(check_consensus("skx_stream_submit", st, false, nullptr));
     if (n_reads == 0) return fail(SKX_ERR_INVALID, "empty batch");
     if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
     for (u32 r = 0; r < n_reads; ++r)
@@ -3375,6 +3452,9 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
             HIPCHK(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
         }
     }
+    if (cons)  // (the first bound submit: a device copy of the codes for every slot)
+        for (u32 si = 0; si < st->n_slots; ++si)
+            if (!st->slot[si].d_cons) HIPCHK(hipMalloc(&st->slot[si].d_cons, consensus_bytes(st, st->max_reads)));
     const u32 ns = st->n_slots;
     skx_stream::Staged& sl = st->slot[st->next_ticket % ns];
     skx_stream::Staged& other = st->slot[(st->next_ticket + ns - 1) % ns];  // (the previous ticket's)
@@ -3391,6 +3471,7 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
     if (n_bases) HIPCHK(hipMemcpyAsync(sl.d_bases, bases + byte0, n_bytes, hipMemcpyHostToDevice, st->hs_copy));
     HIPCHK(hipEventRecord(sl.ev_copy, st->hs_copy));
     sl.pending = true; sl.dropped = false; sl.n_reads = n_reads; sl.n_bases = n_bases; sl.out_idx = topk_idx; sl.out_sum = reinterpret_cast<u64*>(topk_sum);
+    sl.out_cons = cons;
     sl.ticket = st->next_ticket;
     if (ticket) *ticket = st->next_ticket;
     st->next_ticket += 1;
@@ -4113,6 +4194,39 @@ SKX_API int skx_predict_groups(const skx_ref* ref, const uint8_t* bases, const u
         for (u32 g = 0; g < ng; ++g) max_len = std::max(max_len, sl[g]);
         const size_t out_at = (size_t)g0 * n_sp * top_k;
         SKXCHK(rank_sketches_checked(ref, reinterpret_cast<const uint64_t*>(sk), sl, ng, s, top_k, top_idx + out_at, top_shared + out_at, nullptr, max_len));
+    }
+    return SKX_OK;
+}
+
+// Consensus codes of ranked rows that live on the host: checks first, then chunks of rows through the device (kConsRowsBytes of index rows
+// or of codes at a time, whichever is larger per row)
+static const u64 kConsRowsBytes = 64ull << 20;
+SKX_API int skx_consensus_rows(const skx_ref* ref, const uint32_t* idx, uint64_t n_rows, uint32_t top_k, uint32_t* codes_out) {
+    SKXCHK(check_top_range("skx_consensus_rows", top_k));
+    if (!ref || !idx || !codes_out) return fail(SKX_ERR_INVALID, "skx_consensus_rows: NULL argument");
+    if (!ref->d_codes) return fail(SKX_ERR_INVALID, "skx_consensus_rows: the reference has no genotype table");
+    const u32 n_sp = ref->n_species, n_feat = ref->n_features;
+    for (u64 r = 0; r < n_rows; ++r)
+        for (u32 sp = 0; sp < n_sp; ++sp) {
+            const uint32_t* row = idx + (r * n_sp + sp) * top_k;
+            for (u32 j = 0; j < top_k; ++j)
+                if (row[j] >= ref->sp_n[sp])
+                    return fail(SKX_ERR_INVALID, "skx_consensus_rows: row %llu species %u holds index %u >= its n_genomes=%u",
+                                (unsigned long long)r, sp, row[j], ref->sp_n[sp]);
+        }
+    if (n_rows == 0) return SKX_OK;
+    SKXCHK(use_device(ref->device));
+    const u64 row_bytes = (u64)n_sp * std::max(top_k, n_feat) * 4;
+    const u64 chunk = std::min<u64>(n_rows, std::max<u64>(1, kConsRowsBytes / row_bytes));
+    DevMem m_idx, m_out;
+    HIPCHK(m_idx.need((size_t)chunk * n_sp * top_k * 4));
+    HIPCHK(m_out.need((size_t)chunk * n_sp * n_feat * 4));
+    for (u64 r0 = 0; r0 < n_rows; r0 += chunk) {
+        const u64 n = std::min(chunk, n_rows - r0);
+        HIPCHK(hipMemcpy(m_idx.p, idx + r0 * n_sp * top_k, (size_t)n * n_sp * top_k * 4, hipMemcpyHostToDevice));
+        skx::launch_consensus_rows(nullptr, m_idx.as<u32>(), 0, n, n_sp, top_k, ref->d_sp_g0, ref->d_codes, n_feat, m_out.as<u32>(), ref->n_pad);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(codes_out + r0 * n_sp * n_feat, m_out.p, (size_t)n * n_sp * n_feat * 4, hipMemcpyDeviceToHost));
     }
     return SKX_OK;
 }

@@ -5163,6 +5163,50 @@ __global__ __launch_bounds__(256) void cand_rows_back_kernel(u32* __restrict__ o
     if (slot < cap) out_idx[i] = cand[(size_t)spi * cap + slot] - g0[spi];
 }
 
+// ---- consensus genotypes: per (row, species, feature) the code most of the row's top_k genomes carry, ties to the smallest code
+// idx [rows][n_sp][top_k] genome indices local to the species (g0[sp]: the species' first row of the table), codes [n_code_rows][n_feat]
+// genome-major, out [rows][n_sp][n_feat].  One thread per output value: the lanes of a wave sit on consecutive features of the same
+// few table rows (coalesced gathers; the row's indices are a broadcast), nothing is exchanged between lanes, one plain store each.
+// A table row index is clamped to the table, so a row that was never written cannot make the gather leave it.
+// KMAX <= 8 (top_k == KMAX): the codes live in registers, K x K compares.  Larger KMAX (top_k <= KMAX): the codes live in registers,
+// the candidate of the outer loop is read again (same cache line as a moment ago) so that no register is indexed dynamically.
+template <int KMAX, bool EXACT>
+__global__ __launch_bounds__(256) void consensus_rows_kernel(const u32* __restrict__ idx, u32 n_out /* rows x species x features */, u32 n_sp,
+                                                             u32 top_k, const u32* __restrict__ g0, const u32* __restrict__ codes,
+                                                             u32 n_code_rows, u32 n_feat, u32* __restrict__ out) {
+    __builtin_amdgcn_s_setprio(3);
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n_out) return;
+    const u32 rs = i / n_feat;                  // (row, species)
+    const u32 f = i - rs * n_feat;
+    const u32 base = g0[rs % n_sp], last = n_code_rows - 1u;
+    const u32* row = idx + (size_t)rs * top_k;
+    const u32* col = codes + f;
+    const u32 k = EXACT ? (u32)KMAX : top_k;
+    u32 c[KMAX];
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) c[j] = (u32)j < k ? col[(size_t)min(base + row[j], last) * n_feat] : 0u;
+    u32 best = 0xFFFFFFFFu, best_n = 0;
+    if (EXACT) {
+#pragma unroll
+        for (int j = 0; j < KMAX; ++j) {
+            u32 n = 0;
+#pragma unroll
+            for (int m = 0; m < KMAX; ++m) n += c[m] == c[j] ? 1u : 0u;
+            if (n > best_n || (n == best_n && c[j] < best)) { best = c[j]; best_n = n; }
+        }
+    } else {
+        for (u32 j = 0; j < k; ++j) {
+            const u32 cj = col[(size_t)min(base + row[j], last) * n_feat];
+            u32 n = 0;
+#pragma unroll
+            for (int m = 0; m < KMAX; ++m) n += ((u32)m < k && c[m] == cj) ? 1u : 0u;
+            if (n > best_n || (n == best_n && cj < best)) { best = cj; best_n = n; }
+        }
+    }
+    out[i] = best;
+}
+
 // =====================================================================================
 // launchers
 // =====================================================================================
@@ -5498,6 +5542,41 @@ void launch_cand_rows_back(hipStream_t st, u32* out_idx, u32 n_reads, u32 n_sp, 
     const u32 n = n_reads * n_sp * top_k;
     if (n == 0) return;
     hipLaunchKernelGGL(cand_rows_back_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, out_idx, n, n_sp, top_k, cand, cap, g0);
+}
+template <int KMAX, bool EXACT>
+static void consensus_rows_go(hipStream_t st, const u32* idx, u32 n_out, u32 n_sp, u32 top_k, const u32* g0, const u32* codes, u32 n_code_rows,
+                              u32 n_feat, u32* out) {
+    hipLaunchKernelGGL((consensus_rows_kernel<KMAX, EXACT>), dim3(cdiv(n_out, 256)), dim3(256), 0, st, idx, n_out, n_sp, top_k, g0, codes,
+                       n_code_rows, n_feat, out);
+}
+void launch_consensus_rows(hipStream_t st, const u32* idx, u64 first_row, u64 n_rows, u32 n_sp, u32 top_k, const u32* g0, const u32* codes,
+                           u32 n_feat, u32* out, u32 n_code_rows) {
+    if (n_rows == 0 || n_sp == 0 || n_feat == 0 || top_k == 0 || top_k > kConsensusTopMax || n_code_rows == 0) return;
+    const u64 per_launch = std::max<u64>(1, (1ull << 31) / ((u64)n_sp * n_feat));  // (a launch indexes its outputs in 32 bits)
+    if (n_rows > per_launch) {
+        for (u64 r = 0; r < n_rows; r += per_launch)
+            launch_consensus_rows(st, idx, first_row + r, std::min(per_launch, n_rows - r), n_sp, top_k, g0, codes, n_feat, out, n_code_rows);
+        return;
+    }
+    const u32 n_out = (u32)(n_rows * n_sp * n_feat);
+    idx += first_row * n_sp * top_k;
+    out += first_row * n_sp * n_feat;
+#define SKX_CONS(K, E) consensus_rows_go<K, E>(st, idx, n_out, n_sp, top_k, g0, codes, n_code_rows, n_feat, out)
+    switch (top_k) {
+        case 1: SKX_CONS(1, true); break;
+        case 2: SKX_CONS(2, true); break;
+        case 3: SKX_CONS(3, true); break;
+        case 4: SKX_CONS(4, true); break;
+        case 5: SKX_CONS(5, true); break;
+        case 6: SKX_CONS(6, true); break;
+        case 7: SKX_CONS(7, true); break;
+        case 8: SKX_CONS(8, true); break;
+        default:
+            if (top_k <= 16) SKX_CONS(16, false);
+            else if (top_k <= 32) SKX_CONS(32, false);
+            else SKX_CONS(64, false);
+    }
+#undef SKX_CONS
 }
 void launch_window(hipStream_t st, const u64* lo, const u64* hi, u32 n_bt, const u64* q, const u32* n_q, u32* win, u32* h_nq) {
     hipLaunchKernelGGL(window_kernel, dim3(cdiv(n_bt, 256)), dim3(256), 0, st, lo, hi, n_bt, q, n_q, win, h_nq);

@@ -215,6 +215,13 @@ void launch_cand_publish(hipStream_t st, const u32* bad, u32 force_full, const u
 void launch_m_clear(hipStream_t st, u64* m_bits, u64* m_int /* or NULL */, u32 n_pad, const u32* n_d, const u32* any_full);
 void launch_cand_pair_rows(hipStream_t st, const u32* pair_q, u32 n_pairs, const u32* n_d, const u32* smap, u32 rows_c, u32* pair_qc);
 void launch_cand_rows_back(hipStream_t st, u32* out_idx, u32 n_reads, u32 n_sp, u32 top_k, const u32* cand, u32 cap, const u32* g0);
+// consensus genotypes of finished index rows: out[row][sp][f] = the code most of codes[g0[sp] + idx[row][sp][j]][f], j < top_k, carry;
+// ties go to the smallest code.  Rows [first_row, first_row + n_rows) of idx [.][n_sp][top_k] and out [.][n_sp][n_feat];
+// codes [n_code_rows][n_feat] (table rows past the end are clamped to it); 1 <= top_k <= kConsensusTopMax.
+// One thread per output value; more than 2^31 of them go out as several launches.
+constexpr u32 kConsensusTopMax = 64;
+void launch_consensus_rows(hipStream_t st, const u32* idx, u64 first_row, u64 n_rows, u32 n_sp, u32 top_k, const u32* g0, const u32* codes,
+                           u32 n_feat, u32* out, u32 n_code_rows);
 
 // dictionary
 // qrow (launch_classify) != NULL: pair_q receives ROWS of the bit matrix instead of positions in q

@@ -48,6 +48,11 @@ extern "C" int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t
 // ... and so is the device-side ranking of many pooled sketches: without it the host takes skx_common_hashes' counts and sorts.
 extern "C" int skx_rank_sketches(const skx_ref* ref, const uint64_t* query, const uint32_t* query_len, uint32_t n_query, uint32_t q_stride,
                                  uint32_t top_k, uint32_t* top_idx, uint32_t* top_shared, uint32_t* common) __attribute__((weak));
+// ... and the consensus calls on the device (genotype table as codes on the reference, one code per column and read back instead of
+// rows): without them --consensus votes over rows on the host, as before.
+extern "C" int skx_ref_set_genotypes(skx_ref* ref, uint32_t n_features, const uint32_t* codes) __attribute__((weak));
+extern "C" int skx_consensus_rows(const skx_ref* ref, const uint32_t* idx, uint64_t n_rows, uint32_t top_k, uint32_t* codes_out) __attribute__((weak));
+extern "C" int skx_stream_bind_consensus(skx_stream* st, uint32_t* codes_out) __attribute__((weak));
 
 namespace sketchy {
 
@@ -80,6 +85,8 @@ class Sketchy {
         if (config.top > sketches.size()) throw SketchyError("--top exceeds the number of reference sketches");
         if (config.header) out << "reads\tsketch_id\tshared_hashes\t" << geno.header << "\n";  // :99-101
         Ref ref(sketches, device_);
+        cons_ = ConsensusTable();
+        if (config.consensus) set_consensus_table(sketches, ref, geno, config);
         if (config.stream) sum_of_shared_hashes(fastx.empty() ? std::string("-") : fastx[0], sketches, ref, geno, config, out);
         else shared_hashes(fastx.empty() ? std::vector<std::string>{"-"} : fastx, sketches, ref, geno, config, out);
     }
@@ -225,6 +232,53 @@ class Sketchy {
         uint32_t stride_ = 0;
     };
 
+    // --consensus on the device: every genotype column as a dictionary of its distinct strings in byte-wise sorted order (the order
+    // of the std::map print_results votes in), a genome's code = its string's rank.  The library's tie rule -- the smallest code --
+    // is then print_results' "first maximum of the map": the same bytes come out.
+    struct ConsensusTable {
+        bool on = false;
+        size_t nfeat = 0, line_cap = 0;                // columns; bytes a line can take
+        std::vector<std::vector<std::string>> values;  // [column][code]
+    } cons_;
+    void set_consensus_table(const std::vector<Sketch>& sketches, Ref& ref, const Genotypes& geno, const PredictConfig& config) {
+        if (!skx_ref_set_genotypes || !skx_consensus_rows || !skx_stream_bind_consensus) return;  // (a library without them)
+        if (config.top < 1 || config.top > SKX_MAX_TOP) return;
+        const size_t nfeat = geno.map.at(sketches[0].name).size();
+        if (nfeat < 1 || nfeat > SKX_MAX_FEATURES) return;
+        std::vector<const std::vector<std::string>*> rows;
+        for (const auto& sk : sketches) {
+            rows.push_back(&geno.map.at(sk.name));
+            if (rows.back()->size() != nfeat) return;  // (a ragged table: print_results decides what that means)
+        }
+        ConsensusTable t;
+        t.nfeat = nfeat; t.line_cap = 32;
+        std::vector<uint32_t> codes(rows.size() * nfeat);
+        for (size_t j = 0; j < nfeat; ++j) {
+            std::map<std::string, uint32_t> rank;
+            for (const auto* r : rows) rank.emplace((*r)[j], 0u);
+            std::vector<std::string> vals;
+            size_t longest = 0;
+            for (auto& kv : rank) { kv.second = (uint32_t)vals.size(); vals.push_back(kv.first); longest = std::max(longest, kv.first.size()); }
+            for (size_t g = 0; g < rows.size(); ++g) codes[g * nfeat + j] = rank.at((*rows[g])[j]);
+            t.values.push_back(std::move(vals));
+            t.line_cap += longest + 1;
+        }
+        hip_check(skx_ref_set_genotypes(ref.h, (uint32_t)nfeat, codes.data()), "genotype table");
+        t.on = true;
+        cons_ = std::move(t);
+    }
+    // "<read>\t-\t-\t<call>\t...\n" from one read's codes; p has line_cap bytes of room
+    char* put_consensus_line(char* p, size_t read, const uint32_t* codes) const {
+        p = put_u64(p, read);
+        memcpy(p, "\t-\t-\t", 5); p += 5;
+        for (size_t j = 0; j < cons_.nfeat; ++j) {
+            const std::string& v = cons_.values[j][codes[j]];
+            memcpy(p, v.data(), v.size()); p += v.size();
+            *p++ = j + 1 < cons_.nfeat ? '\t' : '\n';
+        }
+        return p;
+    }
+
     struct Batch { std::vector<uint8_t> bases; std::vector<uint64_t> offsets{0}; size_t n() const { return offsets.size() - 1; }
                    void add(const std::string& seq) { bases.insert(bases.end(), seq.begin(), seq.end()); offsets.push_back(bases.size()); }
                    void clear() { bases.clear(); offsets.assign(1, 0); } };
@@ -268,6 +322,7 @@ class Sketchy {
     // which only depends on OLDER chunks, so the ring cannot deadlock.
     struct Slot {
         uint8_t* packed = nullptr; uint64_t* offsets = nullptr; uint32_t* idx = nullptr; uint64_t* sum = nullptr;
+        uint32_t* cons = nullptr;  // consensus on the device: [reads][columns] codes instead of rows
         size_t n = 0, first_read = 1;
         // what did not fit the slot (a chunk with far more / longer reads than the first records promised): heap batches the
         // device thread sends through its spill slot, one by one (rare, slow, correct)
@@ -387,14 +442,16 @@ class Sketchy {
         hip_check(skx_stream_set_packed_input(st, 1), "packed input");
 
         std::vector<Slot> slots(n_slots + 1);  // (+ the device thread's spill slot)
-        struct SlotGuard { std::vector<Slot>& s; int dev; ~SlotGuard() { for (auto& x : s) { for (void* p : {(void*)x.packed, (void*)x.offsets, (void*)x.idx, (void*)x.sum}) if (p) skx_host_free(dev, p); } } } sguard{slots, device_};
-        const size_t rows_cap = cap_reads * config.top;
+        struct SlotGuard { std::vector<Slot>& s; int dev; ~SlotGuard() { for (auto& x : s) { for (void* p : {(void*)x.packed, (void*)x.offsets, (void*)x.idx, (void*)x.sum, (void*)x.cons}) if (p) skx_host_free(dev, p); } } } sguard{slots, device_};
+        const bool dev_cons = config.consensus && cons_.on;  // one code per column and read comes back, no rows
+        const size_t rows_cap = dev_cons ? 0 : cap_reads * config.top;
         for (auto& sl : slots) {
             void* p = nullptr;
             hip_check(skx_host_alloc(device_, &p, cap_bases / 2 + 64), "batch buffer"); sl.packed = static_cast<uint8_t*>(p);
             hip_check(skx_host_alloc(device_, &p, (cap_reads + 1) * 8), "batch buffer"); sl.offsets = static_cast<uint64_t*>(p);
             hip_check(skx_host_alloc(device_, &p, std::max<size_t>(rows_cap, 1) * 4), "row buffer"); sl.idx = static_cast<uint32_t*>(p);
             hip_check(skx_host_alloc(device_, &p, std::max<size_t>(rows_cap, 1) * 8), "row buffer"); sl.sum = static_cast<uint64_t*>(p);
+            if (dev_cons) { hip_check(skx_host_alloc(device_, &p, cap_reads * cons_.nfeat * 4), "consensus buffer"); sl.cons = static_cast<uint32_t*>(p); }
         }
         Slot& spill = slots[n_slots];
 
@@ -561,7 +618,7 @@ class Sketchy {
         }
 
         // ---- stage 3 + 4: rows as text, written in order
-        struct Job { Slot* sl = nullptr; size_t seq = 0, n = 0, first_read = 1; uint64_t ticket = 0; std::vector<uint32_t> idx; std::vector<uint64_t> sum; };
+        struct Job { Slot* sl = nullptr; size_t seq = 0, n = 0, first_read = 1; uint64_t ticket = 0; std::vector<uint32_t> idx, cons; std::vector<uint64_t> sum; };
         std::deque<Job> format_q;
         bool format_closed = false;
         std::map<size_t, std::string> done_text;  // seq -> text, waiting for its turn
@@ -586,7 +643,13 @@ class Sketchy {
                         const uint32_t* idx = job.sl ? job.sl->idx : job.idx.data();
                         const uint64_t* sum = job.sl ? job.sl->sum : job.sum.data();
                         std::string text;
-                        if (config.consensus) {
+                        if (dev_cons) {
+                            const uint32_t* codes = job.sl ? job.sl->cons : job.cons.data();
+                            text.resize(job.n * cons_.line_cap);
+                            char* p = text.data();
+                            for (size_t r = 0; r < job.n; ++r) p = put_consensus_line(p, job.first_read + r, codes + r * cons_.nfeat);
+                            text.resize((size_t)(p - text.data()));
+                        } else if (config.consensus) {
                             std::ostringstream os;
                             for (size_t r = 0; r < job.n; ++r) print_results(sketches, geno, idx + r * config.top, sum + r * config.top, job.first_read + r, config, os);
                             text = os.str();
@@ -644,12 +707,13 @@ class Sketchy {
                     if (stop) break;
                 }
                 const bool last = sl->last;
-                auto submit = [&](const uint8_t* packed, const uint64_t* offsets, size_t n, uint32_t* idx, uint64_t* sum, Slot* owner) {
+                auto submit = [&](const uint8_t* packed, const uint64_t* offsets, size_t n, uint32_t* idx, uint64_t* sum, uint32_t* cons, Slot* owner) {
                     if (config.limit && fed + n >= config.limit) { n = config.limit - fed; limit_hit = true; }  // src/sketchy.rs:350-353
                     if (n == 0) { if (owner) release_slot(owner); return; }
                     uint64_t ticket = 0;
                     const auto ts = clock::now();
-                    hip_check(skx_stream_submit(st, packed, offsets, (uint32_t)n, idx, sum, &ticket), "submit");
+                    if (dev_cons) hip_check(skx_stream_bind_consensus(st, cons), "bind consensus");
+                    hip_check(skx_stream_submit(st, packed, offsets, (uint32_t)n, dev_cons ? nullptr : idx, dev_cons ? nullptr : sum, &ticket), "submit");
                     s_submit += since(ts);
                     Job j; j.sl = owner; j.seq = seq_no++; j.n = n; j.first_read = fed + 1; j.ticket = ticket;
                     fed += n; ++n_batches;
@@ -660,16 +724,17 @@ class Sketchy {
                 };
                 std::vector<Slot::Extra> extra;
                 extra.swap(sl->extra);
-                submit(sl->packed, sl->offsets, sl->n, sl->idx, sl->sum, sl);
+                submit(sl->packed, sl->offsets, sl->n, sl->idx, sl->sum, sl->cons, sl);
                 for (auto& e : extra) {  // the chunk's overflow, through the spill slot: drained each time (rare path)
                     if (limit_hit) break;
                     const size_t n = e.offsets.size() - 1;
                     memcpy(spill.packed, e.packed.data(), std::min(e.packed.size(), cap_bases / 2 + 64));
                     memcpy(spill.offsets, e.offsets.data(), e.offsets.size() * 8);
-                    submit(spill.packed, spill.offsets, n, spill.idx, spill.sum, nullptr);
+                    submit(spill.packed, spill.offsets, n, spill.idx, spill.sum, spill.cons, nullptr);
                     hip_check(skx_stream_drain(st), "drain");
                     Job& j = in_flight.back().second;  // its rows leave the spill slot before the next overflow batch uses it
-                    j.idx.assign(spill.idx, spill.idx + j.n * config.top); j.sum.assign(spill.sum, spill.sum + j.n * config.top);
+                    if (dev_cons) j.cons.assign(spill.cons, spill.cons + j.n * cons_.nfeat);
+                    else { j.idx.assign(spill.idx, spill.idx + j.n * config.top); j.sum.assign(spill.sum, spill.sum + j.n * config.top); }
                     retire(0);
                 }
                 if (last) break;
@@ -746,6 +811,15 @@ class Sketchy {
                 std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b2) { return c[a] > c[b2]; });  // :310
                 for (size_t j = 0; j < config.top; ++j) { idx[f * config.top + j] = order[j]; shared[f * config.top + j] = c[order[j]]; }
             }
+        }
+        if (config.consensus && cons_.on) {  // the vote of all samples in one call, a line each from its codes
+            std::vector<uint32_t> codes(n * cons_.nfeat);
+            hip_check(skx_consensus_rows(ref.h, idx.data(), n, (uint32_t)config.top, codes.data()), "consensus");
+            std::string text(n * cons_.line_cap, '\0');
+            char* p = text.data();
+            for (size_t f = 0; f < n; ++f) p = put_consensus_line(p, reads[f], codes.data() + f * cons_.nfeat);
+            out.write(text.data(), p - text.data());
+            return;
         }
         std::vector<uint64_t> sum(config.top);
         for (size_t f = 0; f < n; ++f) {

@@ -25,6 +25,7 @@
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
  *   skx_sketch_groups      <- finch SketchScheme::{process x many, to_vec}: ONE sketcher fed several records -- all reads of an
  *                             offline `predict` (src/sketchy.rs:291-302), all contigs of a genome file in `sketch` (:473-478)
+ *   skx_sketch_groups_counts <- the same + KmerCount.count of every sketch hash (:302, :480-488): Mash's counts32
  *
  * Conventions: every function returns 0 (SKX_OK) or a negative SKX_ERR_* code and never
  * throws; skx_last_error() returns a thread-local message for the last failure.  Handles
@@ -355,6 +356,15 @@ int skx_sketch_reads(int device, uint32_t k, uint64_t seed, uint32_t s, const ui
 int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t *bases, const uint64_t *offsets,
                       uint32_t n_records, const uint32_t *group_first, uint32_t n_groups,
                       uint64_t *sketches, uint32_t *sketch_len, uint64_t *valid_kmers);
+/* skx_sketch_groups + the abundance of every sketch hash: finch's KmerCount.count (src/sketchy.rs:302, :480-488), what its Mash
+ * writer stores in `counts32`.  counts [n_groups][s], REQUIRED: counts[g][j] = valid k-mer windows (as valid_kmers counts them,
+ * duplicates included) over all records of group g whose canonical hash is sketches[g][j]; 0 for j >= sketch_len[g]; saturating at
+ * 0xFFFFFFFF (the true multiplicity: the width of finch's own counter is not pinned).  Independent of the order of records.
+ * Every other argument, check and result as skx_sketch_groups; counts == NULL is SKX_ERR_INVALID.  The device walks a slice's bases
+ * once more against the slice-local pooled rows and adds the counts of equal hashes wherever rows meet: exact. */
+int skx_sketch_groups_counts(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t *bases, const uint64_t *offsets,
+                             uint32_t n_records, const uint32_t *group_first, uint32_t n_groups, uint64_t *sketches,
+                             uint32_t *sketch_len, uint64_t *valid_kmers, uint32_t *counts);
 /*
  * common[q][g] = |query sketch q  intersect  reference genome g|  (src/sketchy.rs:419-438) for
  * n_query ascending sketches laid out like skx_ref_create's input (row stride q_stride).

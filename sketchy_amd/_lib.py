@@ -70,6 +70,7 @@ SYMBOLS = [
     ("skx_stream_scan_alone", _i, [_vp, C.c_uint32, C.POINTER(C.c_double)]),
     ("skx_sketch_reads", _i, [_i, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _vp]),
     ("skx_sketch_groups", _i, [_i, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp]),
+    ("skx_sketch_groups_counts", _i, [_i, _u32, _u64, _u32, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     ("skx_common_hashes", _i, [_vp, _vp, _vp, _u32, _u32, _vp]),
     ("skx_rank_sketches", _i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("skx_consensus_rows", _i, [_vp, _vp, _u64, _u32, _vp]),

@@ -450,10 +450,11 @@ def sketch_reads(bases, offsets, k=16, seed=0, s=1000, device=0):
     return sk, sl
 
 
-def sketch_groups(bases, offsets, group_first, k=16, seed=0, s=1000, device=0, want_valid_kmers=False):
+def sketch_groups(bases, offsets, group_first, k=16, seed=0, s=1000, device=0, want_valid_kmers=False, want_counts=False):
     """finch MashSketcher fed several records: ONE bottom-s sketch per group of records, pooled on the device.
     Group g = records [group_first[g], group_first[g + 1]).  Returns ([n_groups, s] uint64 ascending zero-padded, lengths
-    [, valid k-mer windows per group])."""
+    [, valid k-mer windows per group][, counts]).  want_counts: the LAST element is [n_groups, s] uint32, counts[g, j] = valid
+    k-mer windows of group g whose hash is sketches[g, j] (finch's KmerCount.count, Mash's counts32), zero beyond the length."""
     bases = np.ascontiguousarray(bases, np.uint8)
     offsets = np.ascontiguousarray(offsets, np.uint64)
     group_first = np.ascontiguousarray(group_first, np.uint32)
@@ -462,6 +463,11 @@ def sketch_groups(bases, offsets, group_first, k=16, seed=0, s=1000, device=0, w
     sl = np.zeros(ng, np.uint32)
     vk = np.zeros(ng, np.uint64) if want_valid_kmers else None
     b = bases if len(bases) else np.zeros(1, np.uint8)
+    if want_counts:
+        kc = np.zeros((ng, s), np.uint32)
+        _lib.check(_lib.load().skx_sketch_groups_counts(device, k, seed, s, _p(b), _p(offsets), n, _p(group_first), ng, _p(sk), _p(sl),
+                                                        _p(vk) if want_valid_kmers else None, _p(kc)))
+        return (sk, sl, vk, kc) if want_valid_kmers else (sk, sl, kc)
     _lib.check(_lib.load().skx_sketch_groups(device, k, seed, s, _p(b), _p(offsets), n, _p(group_first), ng, _p(sk), _p(sl),
                                              _p(vk) if want_valid_kmers else None))
     return (sk, sl, vk) if want_valid_kmers else (sk, sl)

@@ -3851,32 +3851,36 @@ struct DevMem {  // a device allocation that grows on demand and is freed on eve
 }  // namespace
 static u32 ceil_log2(u32 n) { u32 r = 0; while (r < 32 && (1ull << r) < n) ++r; return r; }
 
-SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases, const uint64_t* offsets,
-                              uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
-                              uint32_t* sketch_len, uint64_t* valid_kmers) {
-    if (!offsets) return fail(SKX_ERR_INVALID, "skx_sketch_groups: offsets is NULL");
-    if (!group_first) return fail(SKX_ERR_INVALID, "skx_sketch_groups: group_first is NULL");
-    if (!sketches) return fail(SKX_ERR_INVALID, "skx_sketch_groups: sketches is NULL");
-    if (!sketch_len) return fail(SKX_ERR_INVALID, "skx_sketch_groups: sketch_len is NULL");
-    if (k < 1 || k > SKX_MAX_K) return fail(SKX_ERR_INVALID, "skx_sketch_groups: k = %u outside 1..%u", k, SKX_MAX_K);
-    if (s < 1) return fail(SKX_ERR_INVALID, "skx_sketch_groups: s must be at least 1");
+// skx_sketch_groups (counts == NULL, want_counts false: not one launch, allocation or copy more than before the counts existed)
+// and skx_sketch_groups_counts (fn: the name the messages carry)
+static int sketch_groups_impl(const char* fn, bool want_counts, int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases,
+                              const uint64_t* offsets, uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
+                              uint32_t* sketch_len, uint64_t* valid_kmers, uint32_t* counts) {
+    if (!offsets) return fail(SKX_ERR_INVALID, "%s: offsets is NULL", fn);
+    if (!group_first) return fail(SKX_ERR_INVALID, "%s: group_first is NULL", fn);
+    if (!sketches) return fail(SKX_ERR_INVALID, "%s: sketches is NULL", fn);
+    if (!sketch_len) return fail(SKX_ERR_INVALID, "%s: sketch_len is NULL", fn);
+    if (want_counts && !counts) return fail(SKX_ERR_INVALID, "%s: counts is NULL", fn);
+    if (k < 1 || k > SKX_MAX_K) return fail(SKX_ERR_INVALID, "%s: k = %u outside 1..%u", fn, k, SKX_MAX_K);
+    if (s < 1) return fail(SKX_ERR_INVALID, "%s: s must be at least 1", fn);
     u64 longest = 1;
     for (u32 r = 0; r < n_records; ++r) {
-        if (offsets[r + 1] < offsets[r]) return fail(SKX_ERR_INVALID, "skx_sketch_groups: offsets not monotonic at record %u", r);
+        if (offsets[r + 1] < offsets[r]) return fail(SKX_ERR_INVALID, "%s: offsets not monotonic at record %u", fn, r);
         longest = std::max<u64>(longest, offsets[r + 1] - offsets[r]);
     }
-    if (group_first[0] != 0) return fail(SKX_ERR_INVALID, "skx_sketch_groups: group_first[0] must be 0");
+    if (group_first[0] != 0) return fail(SKX_ERR_INVALID, "%s: group_first[0] must be 0", fn);
     for (u32 g = 0; g < n_groups; ++g)
-        if (group_first[g + 1] < group_first[g]) return fail(SKX_ERR_INVALID, "skx_sketch_groups: group_first decreases at group %u", g);
+        if (group_first[g + 1] < group_first[g]) return fail(SKX_ERR_INVALID, "%s: group_first decreases at group %u", fn, g);
     if (group_first[n_groups] != n_records)
-        return fail(SKX_ERR_INVALID, "skx_sketch_groups: group_first[n_groups] = %u must be n_records = %u", group_first[n_groups], n_records);
-    if (n_records && offsets[n_records] > offsets[0] && !bases) return fail(SKX_ERR_INVALID, "skx_sketch_groups: bases is NULL");
+        return fail(SKX_ERR_INVALID, "%s: group_first[n_groups] = %u must be n_records = %u", fn, group_first[n_groups], n_records);
+    if (n_records && offsets[n_records] > offsets[0] && !bases) return fail(SKX_ERR_INVALID, "%s: bases is NULL", fn);
     if (n_groups == 0) return SKX_OK;
     SKXCHK(use_device(device));
     if (valid_kmers) memset(valid_kmers, 0, (size_t)n_groups * 8);
     if (n_records == 0) {  // every group is empty
         memset(sketches, 0, (size_t)n_groups * s * 8);
         memset(sketch_len, 0, (size_t)n_groups * 4);
+        if (counts) memset(counts, 0, (size_t)n_groups * s * 4);
         return SKX_OK;
     }
     const u32 stride = (u32)std::min<u64>(s, longest);
@@ -3887,6 +3891,11 @@ SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s,
     const u32 out_cap = (u32)std::min<u64>(n_groups, std::max<u64>(1, kPoolOutBytes / ((u64)s * 8)));
 
     DevMem m_b, m_o, m_sk[2], m_len[2], m_cnt, m_lists, m_vk, m_items, m_desc, m_out, m_out_len, m_acc[2], m_acc_len, m_seg, m_seg_sum;
+    // counts: the root rows' counters of a slice (one row of min(s, stride * rows) per segment, seg_at[i] its start), the segments as
+    // the count kernel wants them, the open group's counts beside acc, the counts of the rows that leave
+    DevMem m_kc, m_cseg, m_acc_kc[2], m_out_kc, m_cdesc;
+    std::vector<uint4> csegs, cdesc;
+    std::vector<u64> seg_at;
     std::vector<u64> off;
     std::vector<uint2> items, desc, segs;
     std::vector<u32> round_at, seg_group;
@@ -3904,6 +3913,12 @@ SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s,
         SKX_TRY(m_out.need((size_t)out_cap * s * 8));
         SKX_TRY(m_out_len.need((size_t)out_cap * 4));
         SKX_TRY(m_desc.need((size_t)out_cap * sizeof(uint2)));
+        if (counts) {
+            SKX_TRY(m_acc_kc[0].need((size_t)s * 4));
+            SKX_TRY(m_acc_kc[1].need((size_t)s * 4));
+            SKX_TRY(m_out_kc.need((size_t)out_cap * s * 4));
+            SKX_TRY(m_cdesc.need((size_t)out_cap * sizeof(uint4)));
+        }
         while (r0 < n_records && e == hipSuccess) {
             // ---- the slice: records [r0, r1)
             u32 r1 = r0;
@@ -3963,11 +3978,33 @@ SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s,
                 *row = m_sk[par].as<u64>() + (size_t)sg.x * stride; *len = m_len[par].as<u32>() + sg.x;
             };
             u32* acc_len = m_acc_len.as<u32>();
+            // ---- counts: one more walk over the slice's bases against every segment's root row, while they are resident
+            if (counts && !segs.empty()) {
+                csegs.resize(segs.size()); seg_at.resize(segs.size());
+                u64 total = 0;
+                for (size_t i = 0; i < segs.size(); ++i) {
+                    seg_at[i] = total;
+                    csegs[i] = make_uint4(segs[i].x, segs[i].y, (u32)total, (u32)(total >> 32));
+                    total += std::min<u64>(s, (u64)stride * segs[i].y);
+                }
+                SKX_TRY(m_kc.need((size_t)total * 4));
+                SKX_TRY(m_cseg.need(csegs.size() * sizeof(uint4)));
+                SKX_TRY(hipMemset(m_kc.p, 0, (size_t)total * 4));
+                SKX_TRY(hipMemcpy(m_cseg.p, csegs.data(), csegs.size() * sizeof(uint4), hipMemcpyHostToDevice));
+                skx::launch_pool_count(nullptr, m_b.as<uint8_t>(), m_o.as<u64>(), n, n_bases, k, seed, m_cseg.as<uint4>(), (u32)csegs.size(),
+                                       m_sk[0].as<u64>(), m_sk[1].as<u64>(), m_len[0].as<u32>(), m_len[1].as<u32>(), stride, s, m_kc.as<u32>());
+                SKX_TRY(hipGetLastError());
+            }
             // the open group of the slice before: its partial row + the root of its rows here (always the first segment)
             if (carry) {
                 const u64* row; const u32* len;
                 root(segs[0], &row, &len);
-                skx::launch_pool_merge_one(nullptr, m_acc[cur].as<u64>(), acc_len + cur, row, len, m_acc[cur ^ 1].as<u64>(), acc_len + (cur ^ 1), s);
+                if (counts)
+                    skx::launch_pool_merge_one_counted(nullptr, m_acc[cur].as<u64>(), m_acc_kc[cur].as<u32>(), acc_len + cur, row,
+                                                       m_kc.as<u32>() + seg_at[0], len, m_acc[cur ^ 1].as<u64>(), m_acc_kc[cur ^ 1].as<u32>(),
+                                                       acc_len + (cur ^ 1), s);
+                else
+                    skx::launch_pool_merge_one(nullptr, m_acc[cur].as<u64>(), acc_len + cur, row, len, m_acc[cur ^ 1].as<u64>(), acc_len + (cur ^ 1), s);
                 cur ^= 1;
             }
             // ---- valid k-mers: per record, then per segment
@@ -3987,9 +4024,24 @@ SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s,
             for (u32 g = g_out; g < g_end && e == hipSuccess; g += out_cap) {
                 const u32 cnt = std::min(out_cap, g_end - g);
                 desc.assign(cnt, make_uint2(0, 0));
+                if (counts) cdesc.assign(cnt, make_uint4(0, 0, 0, 0));
                 for (u32 i = 0; i < cnt; ++i) {
                     while (si < segs.size() && seg_group[si] < g + i) ++si;
-                    if (si < segs.size() && seg_group[si] == g + i) desc[i] = (carry && g + i == g_out) ? make_uint2(0xFFFFFFFFu, 1u) : segs[si];
+                    if (si < segs.size() && seg_group[si] == g + i) {
+                        desc[i] = (carry && g + i == g_out) ? make_uint2(0xFFFFFFFFu, 1u) : segs[si];
+                        if (counts) cdesc[i] = make_uint4(desc[i].x, desc[i].y, (u32)seg_at[si], (u32)(seg_at[si] >> 32));
+                    }
+                }
+                if (counts) {  // the counted gather takes the place of the plain one
+                    SKX_TRY(hipMemcpy(m_cdesc.p, cdesc.data(), (size_t)cnt * sizeof(uint4), hipMemcpyHostToDevice));
+                    skx::launch_pool_gather_counted(nullptr, m_cdesc.as<uint4>(), cnt, m_sk[0].as<u64>(), m_sk[1].as<u64>(), m_len[0].as<u32>(),
+                                                    m_len[1].as<u32>(), stride, m_kc.as<u32>(), m_acc[cur].as<u64>(), m_acc_kc[cur].as<u32>(),
+                                                    acc_len + cur, m_out.as<u64>(), m_out_kc.as<u32>(), m_out_len.as<u32>(), s);
+                    SKX_TRY(hipGetLastError());
+                    SKX_TRY(hipMemcpy(sketches + (size_t)g * s, m_out.p, (size_t)cnt * s * 8, hipMemcpyDeviceToHost));
+                    SKX_TRY(hipMemcpy(sketch_len + g, m_out_len.p, (size_t)cnt * 4, hipMemcpyDeviceToHost));
+                    SKX_TRY(hipMemcpy(counts + (size_t)g * s, m_out_kc.p, (size_t)cnt * s * 4, hipMemcpyDeviceToHost));
+                    continue;
                 }
                 SKX_TRY(hipMemcpy(m_desc.p, desc.data(), (size_t)cnt * sizeof(uint2), hipMemcpyHostToDevice));
                 skx::launch_pool_gather(nullptr, m_desc.as<uint2>(), cnt, m_sk[0].as<u64>(), m_sk[1].as<u64>(), m_len[0].as<u32>(), m_len[1].as<u32>(),
@@ -4006,6 +4058,9 @@ SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s,
                     root(segs.back(), &row, &len);
                     SKX_TRY(hipMemcpy(acc_len + cur, len, 4, hipMemcpyDeviceToDevice));
                     SKX_TRY(hipMemcpy(m_acc[cur].p, row, (size_t)std::min<u64>(s, (u64)segs.back().y * stride) * 8, hipMemcpyDeviceToDevice));
+                    if (counts)
+                        SKX_TRY(hipMemcpy(m_acc_kc[cur].p, m_kc.as<u32>() + seg_at.back(), (size_t)std::min<u64>(s, (u64)segs.back().y * stride) * 4,
+                                          hipMemcpyDeviceToDevice));
                 }
                 carry = true;
             } else {
@@ -4017,8 +4072,21 @@ SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s,
         }
     } while (0);
 #undef SKX_TRY
-    if (e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_sketch_groups: %s", hipGetErrorString(e));
+    if (e != hipSuccess) rc = fail(SKX_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
     return rc;
+}
+
+SKX_API int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases, const uint64_t* offsets,
+                              uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
+                              uint32_t* sketch_len, uint64_t* valid_kmers) {
+    return sketch_groups_impl("skx_sketch_groups", false, device, k, seed, s, bases, offsets, n_records, group_first, n_groups, sketches,
+                              sketch_len, valid_kmers, nullptr);
+}
+SKX_API int skx_sketch_groups_counts(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases, const uint64_t* offsets,
+                                     uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
+                                     uint32_t* sketch_len, uint64_t* valid_kmers, uint32_t* counts) {
+    return sketch_groups_impl("skx_sketch_groups_counts", true, device, k, seed, s, bases, offsets, n_records, group_first, n_groups, sketches,
+                              sketch_len, valid_kmers, counts);
 }
 
 SKX_API int skx_common_hashes(const skx_ref* ref, const uint64_t* query, const uint32_t* query_len, uint32_t n_query,

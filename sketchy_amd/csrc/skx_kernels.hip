@@ -5992,6 +5992,222 @@ __global__ __launch_bounds__(256) void pool_seg_sum_kernel(const u64* __restrict
     if (threadIdx.x == 0u) out[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
+// ---- k-mer abundance counts of the pooled rows (skx_sketch_groups_counts)
+// counts[position j of a segment's root row] = valid k-mer windows of the segment's records whose canonical hash is the row's j-th
+// value.  A segment = a group's records inside the slice; after the merge tree its root row (<= s values) lies at its first row in
+// buffer (ceil(log2(rows)) & 1).  Every hash of the group's FINAL row that occurs in the segment is in that root row (the final
+// row's largest value is <= the root row's largest value, or the root row holds everything), so counting against the root row
+// and adding the counts of equal hashes whenever rows are merged later is exact -- no second sweep once the group is complete.
+//
+// One more walk over the slice's bases, cut into chunks of kCountChunk bytes per workgroup whatever the records' lengths (a
+// contig of megabases next to reads of hundreds of bases); a lane takes kCountLane contiguous bytes and owns the windows that END
+// in them.  It finds its record by bisection over the offsets, walks back over at most k - 1 retained bases to rebuild the run it
+// starts in (whitespace may sit inside a window, so the walk is over retained bases, not bytes), then rolls the forward and
+// reverse-complement codes base by base and hashes every complete window with the sketchers' hash_canonical_packed.  A hash above
+// the root row's last value is dropped (most windows, once the union is larger than s); the others are bisected in the row
+// (<= s values: L2-resident) and a hit adds 1 to the position's counter with a no-return atomic.  A slice holds at most 1 GiB of
+// bases, so a 32-bit counter cannot wrap inside a slice.  Equal positions are NOT aggregated inside the wave first: low-complexity
+// input sends every lane's add to one address, which serialises in L2 -- correct, and (70 000 x A: 140 000 adds) far below the
+// cost of the upload that precedes it.
+// seg[i] = {first row, rows, offset of its counters in `counts` (low, high word)}; the segments tile the slice's records.
+constexpr u32 kCountLane = 128;                  // bytes of a lane
+constexpr u32 kCountChunk = 256u * kCountLane;   // bytes of a workgroup
+
+template <int KT>
+__global__ __launch_bounds__(256) void pool_count_kernel(const uint8_t* __restrict__ bases, const u64* __restrict__ offsets, u32 n_records,
+                                                         u64 n_bases, u32 k_rt, u64 seed, const uint4* __restrict__ seg, u32 n_seg,
+                                                         const u64* __restrict__ buf0, const u64* __restrict__ buf1,
+                                                         const u32* __restrict__ len0, const u32* __restrict__ len1, u32 stride, u32 s,
+                                                         u32* __restrict__ counts) {
+    const u32 k = KT > 0 ? (u32)KT : k_rt;
+    const u64 p0 = ((u64)blockIdx.x * 256u + threadIdx.x) * kCountLane;
+    if (p0 >= n_bases) return;
+    const u64 p1 = min(n_bases, p0 + kCountLane);
+    // the record that holds byte p0: offsets[r] <= p0 < offsets[r + 1] (offsets[0] = 0, offsets[n_records] = n_bases > p0)
+    u32 lo = 0, hi = n_records;  // offsets[lo] <= p0 < offsets[hi] throughout (empty records share an offset: skipped)
+    while (lo + 1u < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (offsets[mid] <= p0) lo = mid; else hi = mid;
+    }
+    u32 r = lo;
+    u64 rec0 = offsets[r], rec1 = offsets[r + 1u];
+    u32 si = 0;                // the record's segment
+    const u64* row = nullptr;  // its root row, n_row values, the last one is thr
+    u32 n_row = 0;
+    u64 thr = 0;
+    u32* cnt = nullptr;
+    auto enter_segment = [&]() {
+        u32 a = si, b = n_seg;  // last segment whose first row is <= r (records only move forward)
+        while (a + 1u < b) {
+            const u32 mid = (a + b) >> 1;
+            if (seg[mid].x <= r) a = mid; else b = mid;
+        }
+        si = a;
+        const uint4 sg = seg[si];
+        const bool odd = (pool_rounds(sg.y) & 1u) != 0u;
+        row = (odd ? buf1 : buf0) + (size_t)sg.x * stride;
+        n_row = min((odd ? len1 : len0)[sg.x], s);
+        thr = n_row ? row[n_row - 1u] : 0ull;
+        cnt = counts + make_u64(sg.z, sg.w);
+    };
+    enter_segment();
+    const u64 mask = k >= 32u ? ~0ull : ((1ull << (2u * k)) - 1ull);
+    u64 fwd = 0, rc = 0;
+    u32 run = 0;
+    for (u64 p = p0; p > rec0 && run < k - 1u; --p) {  // the run the lane starts in: most recent base first
+        const u32 c = classify_base(bases[p - 1u]);
+        if (c == 5u) continue;
+        if (c > 3u) break;
+        fwd |= (u64)c << (2u * run);
+        rc |= (u64)(3u - c) << (2u * (k - 1u - run));
+        ++run;
+    }
+    for (u64 p = p0; p < p1; ++p) {
+        if (p >= rec1) {  // the next record that has bytes: no window spans two records
+            do { ++r; rec1 = offsets[r + 1u]; } while (rec1 <= p);
+            rec0 = offsets[r];
+            run = 0; fwd = 0; rc = 0;
+            enter_segment();
+        }
+        const u32 c = classify_base(bases[p]);
+        if (c == 5u) continue;
+        if (c > 3u) { run = 0; fwd = 0; rc = 0; continue; }
+        fwd = ((fwd << 2) | c) & mask;
+        rc = (rc >> 2) | ((u64)(3u - c) << (2u * (k - 1u)));
+        run = min(run + 1u, k);
+        if (run < k || n_row == 0u) continue;
+        const u64 h = hash_canonical_packed<KT>(fwd < rc ? fwd : rc, k, seed);
+        if (h > thr) continue;
+        u32 a = 0, b = n_row;  // first position whose value is >= h
+        while (a < b) {
+            const u32 mid = (a + b) >> 1;
+            if (row[mid] < h) a = mid + 1u; else b = mid;
+        }
+        if (a < n_row && row[a] == h) atomicAdd(cnt + a, 1u);  // (result unused: a no-return global atomic)
+    }
+}
+
+// pool_merge_rows with counts: the counts travel with their values and the counts of a value both rows hold are added
+// (saturating at 0xFFFFFFFF); what the cut at s drops takes its counts along.  Same tiling as pool_merge_rows; the copy of an equal
+// value from B directly follows the one from A in merged order, and the B window in LDS always holds it (fewer than kPoolTile
+// elements of B precede it in the tile, or the window is all that is left of B), so the kept element finds its partner's count
+// there even when the partner itself falls into the next tile.
+struct PoolCountLds { u32 ca[kPoolTile]; u32 cb[kPoolTile]; };
+
+__device__ __forceinline__ u32 pool_merge_rows_counted(PoolLds& L, PoolCountLds& LC, const u64* __restrict__ A, const u32* __restrict__ CA, u32 na,
+                                                       const u64* __restrict__ B, const u32* __restrict__ CB, u32 nb, u64* __restrict__ dst,
+                                                       u32* __restrict__ dst_cnt, u32 s) {
+    const u32 tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    u32 a0 = 0, b0 = 0, outn = 0;
+    u64 last = 0;
+    bool has_last = false;
+    while (outn < s && (a0 < na || b0 < nb)) {  // (block-uniform)
+        const u32 ca = min(kPoolTile, na - a0), cb = min(kPoolTile, nb - b0);
+        const u32 total = min(kPoolTile, ca + cb);
+        __syncthreads();
+        if (tid < ca) { L.a[tid] = A[a0 + tid]; LC.ca[tid] = CA[a0 + tid]; }
+        if (tid < cb) { L.b[tid] = B[b0 + tid]; LC.cb[tid] = CB[b0 + tid]; }
+        __syncthreads();
+        bool keep = false;
+        u64 v = 0;
+        u32 c = 0;
+        if (tid < total) {
+            u32 lo = tid > cb ? tid - cb : 0u, hi = min(tid, ca);
+            while (lo < hi) {
+                const u32 mid = (lo + hi) >> 1;
+                if (L.a[mid] <= L.b[tid - 1u - mid]) lo = mid + 1u; else hi = mid;
+            }
+            const u32 i = lo, j = tid - lo;
+            const bool from_a = j >= cb || (i < ca && L.a[i] <= L.b[j]);
+            v = from_a ? L.a[i] : L.b[j];
+            c = from_a ? LC.ca[i] : LC.cb[j];
+            if (from_a && j < cb && L.b[j] == v) {
+                const u64 sum = (u64)c + LC.cb[j];
+                c = sum > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)sum;
+            }
+            u64 pred = last;
+            bool has_pred = has_last;
+            if (tid > 0u) {
+                has_pred = true;
+                pred = 0;
+                if (i > 0u) pred = L.a[i - 1u];
+                if (j > 0u) pred = max(pred, L.b[j - 1u]);
+            }
+            keep = !(has_pred && pred == v);
+            if (tid == total - 1u) { L.used_a = i + (from_a ? 1u : 0u); L.last = v; }
+        }
+        const u64 km = __ballot(keep);
+        if (lane == 0u) L.wave_cnt[wave] = (u32)__popcll(km);
+        __syncthreads();
+        u32 before = 0, all = 0;
+#pragma unroll
+        for (u32 w = 0; w < 4u; ++w) { const u32 n = L.wave_cnt[w]; before += w < wave ? n : 0u; all += n; }
+        const u32 pos = outn + before + (u32)__popcll(km & lanemask_lt());
+        if (keep && pos < s) { dst[pos] = v; dst_cnt[pos] = c; }
+        outn += all;
+        const u32 ua = L.used_a;
+        a0 += ua; b0 += total - ua;
+        last = L.last; has_last = true;
+    }
+    return min(outn, s);
+}
+// the carry of the counted call: a group's partial row from the slice before + the root of its rows in this slice, with counts
+__global__ __launch_bounds__(256) void pool_merge_one_counted_kernel(const u64* __restrict__ A, const u32* __restrict__ CA, const u32* __restrict__ na,
+                                                                     const u64* __restrict__ B, const u32* __restrict__ CB, const u32* __restrict__ nb,
+                                                                     u64* __restrict__ dst, u32* __restrict__ dst_cnt, u32* __restrict__ dst_len, u32 s) {
+    __shared__ PoolLds L;
+    __shared__ PoolCountLds LC;
+    const u32 n = pool_merge_rows_counted(L, LC, A, CA, min(*na, s), B, CB, min(*nb, s), dst, dst_cnt, s);
+    if (threadIdx.x == 0u) *dst_len = n;
+}
+// pool_gather_kernel + the rows' counts: desc[g] = {first row, rows, offset of the root row's counters (low, high word)}; first row
+// = 0xFFFFFFFF: the row is acc / acc_cnt.  out_cnt[g][s] zero-padded like out.
+__global__ __launch_bounds__(256) void pool_gather_counted_kernel(const uint4* __restrict__ desc, const u64* __restrict__ buf0, const u64* __restrict__ buf1,
+                                                                  const u32* __restrict__ len0, const u32* __restrict__ len1, u32 stride,
+                                                                  const u32* __restrict__ counts, const u64* __restrict__ acc,
+                                                                  const u32* __restrict__ acc_cnt, const u32* __restrict__ acc_len,
+                                                                  u64* __restrict__ out, u32* __restrict__ out_cnt, u32* __restrict__ out_len, u32 s) {
+    const uint4 d = desc[blockIdx.x];
+    const u64* src = nullptr;
+    const u32* csrc = nullptr;
+    u32 n = 0;
+    if (d.x == 0xFFFFFFFFu) { src = acc; csrc = acc_cnt; n = *acc_len; }
+    else if (d.y != 0u) {
+        const bool odd = (pool_rounds(d.y) & 1u) != 0u;
+        src = (odd ? buf1 : buf0) + (size_t)d.x * stride;
+        csrc = counts + make_u64(d.z, d.w);
+        n = (odd ? len1 : len0)[d.x];
+    }
+    n = min(n, s);
+    u64* o = out + (size_t)blockIdx.x * s;
+    u32* oc = out_cnt + (size_t)blockIdx.x * s;
+    for (u32 i = threadIdx.x; i < s; i += blockDim.x) { o[i] = i < n ? src[i] : 0ull; oc[i] = i < n ? csrc[i] : 0u; }
+    if (threadIdx.x == 0u) out_len[blockIdx.x] = n;
+}
+
+void launch_pool_count(hipStream_t st, const uint8_t* bases, const u64* offsets, u32 n_records, u64 n_bases, u32 k, u64 seed, const uint4* seg,
+                       u32 n_seg, const u64* buf0, const u64* buf1, const u32* len0, const u32* len1, u32 stride, u32 s, u32* counts) {
+    if (n_records == 0 || n_bases == 0 || n_seg == 0) return;
+    const dim3 grid((u32)((n_bases + kCountChunk - 1u) / kCountChunk));
+    if (k == 16)
+        hipLaunchKernelGGL(pool_count_kernel<16>, grid, dim3(256), 0, st, bases, offsets, n_records, n_bases, k, seed, seg, n_seg, buf0, buf1, len0,
+                           len1, stride, s, counts);
+    else
+        hipLaunchKernelGGL(pool_count_kernel<0>, grid, dim3(256), 0, st, bases, offsets, n_records, n_bases, k, seed, seg, n_seg, buf0, buf1, len0,
+                           len1, stride, s, counts);
+}
+void launch_pool_merge_one_counted(hipStream_t st, const u64* a, const u32* ca, const u32* na, const u64* b, const u32* cb, const u32* nb, u64* dst,
+                                   u32* dst_cnt, u32* dst_len, u32 s) {
+    hipLaunchKernelGGL(pool_merge_one_counted_kernel, dim3(1), dim3(256), 0, st, a, ca, na, b, cb, nb, dst, dst_cnt, dst_len, s);
+}
+void launch_pool_gather_counted(hipStream_t st, const uint4* desc, u32 n_groups, const u64* buf0, const u64* buf1, const u32* len0, const u32* len1,
+                                u32 stride, const u32* counts, const u64* acc, const u32* acc_cnt, const u32* acc_len, u64* out, u32* out_cnt,
+                                u32* out_len, u32 s) {
+    if (n_groups == 0) return;
+    hipLaunchKernelGGL(pool_gather_counted_kernel, dim3(n_groups), dim3(256), 0, st, desc, buf0, buf1, len0, len1, stride, counts, acc, acc_cnt,
+                       acc_len, out, out_cnt, out_len, s);
+}
+
 void launch_pool_merge_round(hipStream_t st, const uint2* items, u32 n_items, const u64* src, const u32* src_len, u64* dst, u32* dst_len,
                              u32 stride, u32 s) {
     if (n_items == 0) return;

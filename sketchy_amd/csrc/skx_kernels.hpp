@@ -375,5 +375,18 @@ void launch_pool_gather(hipStream_t st, const uint2* desc, u32 n_groups, const u
 void launch_pool_valid_kmers(hipStream_t st, const uint8_t* bases, const u64* offsets, u32 n_records, u32 k, u64* valid);
 // out[i] = sum of v[seg[i].x .. seg[i].x + seg[i].y)
 void launch_pool_seg_sum(hipStream_t st, const u64* v, const uint2* seg, u32 n_seg, u64* out);
+// k-mer abundance counts (skx_sketch_groups_counts).  seg[i] = {first row, rows, offset of the segment's counters in `counts` (low,
+// high word)}: the segments tile the slice's n_records records in order; a segment's root row sits where launch_pool_gather finds
+// it and its counters (zero on entry, min(s, stride * rows) of them) receive, per position of the root row, the valid k-mer
+// windows of the segment's records whose canonical hash is that value.  offsets[0] = 0, offsets[n_records] = n_bases <= 2^32 - 1.
+void launch_pool_count(hipStream_t st, const uint8_t* bases, const u64* offsets, u32 n_records, u64 n_bases, u32 k, u64 seed, const uint4* seg,
+                       u32 n_seg, const u64* buf0, const u64* buf1, const u32* len0, const u32* len1, u32 stride, u32 s, u32* counts);
+// launch_pool_merge_one with counts: the counts of a value both rows hold are added (saturating), the cut at s drops counts too
+void launch_pool_merge_one_counted(hipStream_t st, const u64* a, const u32* ca, const u32* na, const u64* b, const u32* cb, const u32* nb, u64* dst,
+                                   u32* dst_cnt, u32* dst_len, u32 s);
+// launch_pool_gather + out_cnt[g][s] (zero-padded): desc[g] = {first row, rows, offset of the row's counters (low, high word)}
+void launch_pool_gather_counted(hipStream_t st, const uint4* desc, u32 n_groups, const u64* buf0, const u64* buf1, const u32* len0, const u32* len1,
+                                u32 stride, const u32* counts, const u64* acc, const u32* acc_cnt, const u32* acc_len, u64* out, u32* out_cnt,
+                                u32* out_len, u32 s);
 
 }  // namespace skx

@@ -38,6 +38,7 @@ struct Sketch {  // the fields of finch::serialization::Sketch the path touches
     std::string name, comment;
     uint64_t seq_length = 0, num_valid_kmers = 0;
     std::vector<uint64_t> hashes;  // ascending
+    std::vector<uint32_t> counts;  // finch KmerCount.count / Mash counts32: occurrences of hashes[i] among the k-mers; empty = none
     uint32_t kmer_length = 0;
     uint64_t hash_seed = 0;
 };
@@ -143,6 +144,14 @@ class CapnpMessage {
         for (uint64_t i = 0; i < l.count; ++i) v[i] = word({l.at.seg, l.at.off + i});
         return v;
     }
+    std::vector<uint32_t> list_u32(const Obj& l) const {
+        std::vector<uint32_t> v;
+        if (l.kind != 1 || l.elem_code != 4) return v;
+        check_span(l, (l.count + 1) / 2);
+        v.resize((size_t)l.count);
+        for (uint64_t i = 0; i < l.count; ++i) v[i] = (uint32_t)(word({l.at.seg, l.at.off + i / 2}) >> (32 * (i % 2)));
+        return v;
+    }
   private:
     std::vector<uint64_t> words;
     std::vector<uint64_t> seg_off, seg_len;
@@ -190,10 +199,32 @@ inline std::vector<Sketch> read_mash_file(const std::string& path) {
                 throw std::runtime_error("sketch '" + s.name + "' in " + path + " stores 32-bit hashes only (hashes32: a Mash sketch with k <= 16); "
                                          "this reader, like finch's, takes hashes64 -- build the reference with `sketchy sketch` (64-bit hashes)");
         }
+        s.counts = m.list_u32(m.ptr(r, 6));            // counts32: one count per hash, or absent
+        if (!s.counts.empty() && s.counts.size() != s.hashes.size())
+            throw std::runtime_error("sketch '" + s.name + "' in " + path + " has " + std::to_string(s.counts.size()) + " counts (counts32) for " +
+                                     std::to_string(s.hashes.size()) + " hashes (hashes64)");
         s.kmer_length = kmer; s.hash_seed = seed;
         out.push_back(std::move(s));
     }
     return out;
+}
+
+// Two ascending distinct rows with their counts -> the first s values of their union; the counts of a value both rows hold are
+// added, saturating at 0xFFFFFFFF; what the cut at s drops takes its counts along (the host side of `sketch --counts` for a file
+// larger than a batch: the device does the same where a group is open across slices).
+inline void merge_counted(const uint64_t* a, const uint32_t* ca, size_t na, const uint64_t* b, const uint32_t* cb, size_t nb, size_t s,
+                          std::vector<uint64_t>& out, std::vector<uint32_t>& out_counts) {
+    out.clear(); out_counts.clear();
+    size_t i = 0, j = 0;
+    while (out.size() < s && (i < na || j < nb)) {
+        if (j >= nb || (i < na && a[i] < b[j])) { out.push_back(a[i]); out_counts.push_back(ca[i]); ++i; }
+        else if (i >= na || b[j] < a[i]) { out.push_back(b[j]); out_counts.push_back(cb[j]); ++j; }
+        else {
+            const uint64_t sum = (uint64_t)ca[i] + cb[j];
+            out.push_back(a[i]); out_counts.push_back(sum > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sum);
+            ++i; ++j;
+        }
+    }
 }
 
 // single-segment writer (tests, and `sketch`-style output later)
@@ -229,6 +260,12 @@ inline void write_mash_file(const std::string& path, const std::vector<Sketch>& 
         const size_t at = w.size();
         w.insert(w.end(), sk[i].hashes.begin(), sk[i].hashes.end());
         w[e + 3 + 5] = list_ptr((int64_t)at - (int64_t)(e + 3 + 5) - 1, 5, sk[i].hashes.size());
+        if (!sk[i].counts.empty() && sk[i].counts.size() == sk[i].hashes.size()) {  // counts32: 4-byte elements, two per word
+            const size_t cat = w.size(); const uint64_t cnt = sk[i].counts.size();
+            w.resize(cat + (cnt + 1) / 2, 0);
+            memcpy(&w[cat], sk[i].counts.data(), cnt * 4);
+            w[e + 3 + 6] = list_ptr((int64_t)cat - (int64_t)(e + 3 + 6) - 1, 4, cnt);
+        }
     }
     if (w.size() - 1 >= (1ull << 29)) throw std::runtime_error("sketch too large for the single-segment writer");
     std::ofstream f(path, std::ios::binary);

@@ -45,6 +45,11 @@
 extern "C" int skx_sketch_groups(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases, const uint64_t* offsets,
                                  uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
                                  uint32_t* sketch_len, uint64_t* valid_kmers) __attribute__((weak));
+// ... so is its counted form (`sketch --counts`: the abundance of every sketch hash, Mash's counts32): a library without it cannot
+// fill the list, and --counts says so instead of writing a file without counts.
+extern "C" int skx_sketch_groups_counts(int device, uint32_t k, uint64_t seed, uint32_t s, const uint8_t* bases, const uint64_t* offsets,
+                                        uint32_t n_records, const uint32_t* group_first, uint32_t n_groups, uint64_t* sketches,
+                                        uint32_t* sketch_len, uint64_t* valid_kmers, uint32_t* counts) __attribute__((weak));
 // ... and so is the device-side ranking of many pooled sketches: without it the host takes skx_common_hashes' counts and sorts.
 extern "C" int skx_rank_sketches(const skx_ref* ref, const uint64_t* query, const uint32_t* query_len, uint32_t n_query, uint32_t q_stride,
                                  uint32_t top_k, uint32_t* top_idx, uint32_t* top_shared, uint32_t* common) __attribute__((weak));
@@ -135,7 +140,10 @@ class Sketchy {
     // records per file: the device sketches every record (genomes take the block-per-read + segmented-sort path), pools the
     // rows of a group and counts its valid k-mers (skx_sketch_groups) -- one row of s hashes per file comes back.  A file
     // larger than a batch is cut at record boundaries and its per-batch rows are merged here.
-    void sketch(const std::vector<std::string>& files, const std::string& output, size_t sketch_size, uint32_t kmer, uint64_t seed) {
+    // want_counts (--counts): every hash's abundance as well (skx_sketch_groups_counts), written as the references' counts32; the
+    // per-batch rows of a large file are merged with their counts (merge_counted).
+    void sketch(const std::vector<std::string>& files, const std::string& output, size_t sketch_size, uint32_t kmer, uint64_t seed,
+                bool want_counts = false) {
         const auto dot = output.rfind('.');
         const std::string ext = dot == std::string::npos ? "" : output.substr(dot + 1);
         if (ext == "fsh") throw SketchyError("Finch scaled sketches (.fsh) are outside the accelerated path");
@@ -144,19 +152,29 @@ class Sketchy {
         if (sketch_size > 0xFFFFFFFFull) throw SketchyError("sketch size must fit 32 bits");
         if (kmer < 1 || kmer > SKX_MAX_K) throw SketchyError("k-mer size must be between 1 and " + std::to_string(SKX_MAX_K));
         if (seed > 0xFFFFFFFFull) throw SketchyError("the Mash format stores a 32-bit hash seed");
+        if (want_counts && !skx_sketch_groups_counts)
+            throw SketchyError("--counts needs skx_sketch_groups_counts, which the loaded libsketchy_hip does not export");
         constexpr size_t kBatchBases = 1ull << 30, kBatchRecords = 1ull << 22;
         std::vector<Sketch> out(files.size());
         Batch b; std::string seq;
         std::vector<uint32_t> first, len; std::vector<size_t> owner;  // group g of the batch = records [first[g], first[g + 1]) of file owner[g]
         std::vector<uint64_t> rows, valid, merged;
+        std::vector<uint32_t> counts, merged_counts;
         auto flush = [&]() {
             if (owner.empty()) return;
             first.push_back((uint32_t)b.n());
-            pool_groups(b, first, kmer, seed, (uint32_t)sketch_size, true, rows, len, valid);
+            pool_groups(b, first, kmer, seed, (uint32_t)sketch_size, true, rows, len, valid, want_counts ? &counts : nullptr);
             for (size_t g = 0; g < owner.size(); ++g) {
                 Sketch& sk = out[owner[g]];
                 const uint64_t* row = rows.data() + g * sketch_size;
                 sk.num_valid_kmers += valid[g];  // [UPSTREAM-RECALL] finch: k-mers pushed to the sketcher
+                if (want_counts) {
+                    const uint32_t* cnt = counts.data() + g * sketch_size;
+                    if (sk.hashes.empty()) { sk.hashes.assign(row, row + len[g]); sk.counts.assign(cnt, cnt + len[g]); continue; }
+                    merge_counted(sk.hashes.data(), sk.counts.data(), sk.hashes.size(), row, cnt, len[g], sketch_size, merged, merged_counts);
+                    sk.hashes.swap(merged); sk.counts.swap(merged_counts);
+                    continue;
+                }
                 if (sk.hashes.empty()) { sk.hashes.assign(row, row + len[g]); continue; }
                 merged.clear();
                 std::set_union(sk.hashes.begin(), sk.hashes.end(), row, row + len[g], std::back_inserter(merged));
@@ -285,10 +303,17 @@ class Sketchy {
 
     // One pooled bottom-s row per group of the batch's records (group g = records [first[g], first[g + 1])): rows [groups][s]
     // zero-padded, their lengths and -- want_valid -- the groups' valid k-mer windows.
+    // counts (or NULL): the hashes' abundances [groups][s] as well; the caller has made sure the library has the counted entry point
     void pool_groups(const Batch& b, const std::vector<uint32_t>& first, uint32_t k, uint64_t seed, uint32_t s, bool want_valid,
-                     std::vector<uint64_t>& rows, std::vector<uint32_t>& len, std::vector<uint64_t>& valid) {
+                     std::vector<uint64_t>& rows, std::vector<uint32_t>& len, std::vector<uint64_t>& valid, std::vector<uint32_t>* counts = nullptr) {
         const size_t ng = first.size() - 1;
         rows.assign(ng * (size_t)s, 0); len.assign(ng, 0); valid.assign(ng, 0);
+        if (counts) {
+            counts->assign(ng * (size_t)s, 0);
+            hip_check(skx_sketch_groups_counts(device_, k, seed, s, b.bases.data(), b.offsets.data(), (uint32_t)b.n(), first.data(), (uint32_t)ng,
+                                               rows.data(), len.data(), want_valid ? valid.data() : nullptr, counts->data()), "sketch");
+            return;
+        }
         if (skx_sketch_groups) {
             hip_check(skx_sketch_groups(device_, k, seed, s, b.bases.data(), b.offsets.data(), (uint32_t)b.n(), first.data(), (uint32_t)ng,
                                         rows.data(), len.data(), want_valid ? valid.data() : nullptr), "sketch");
@@ -857,7 +882,8 @@ class Sketchy {
 // ------------------------------------------------------------------ command line (src/cli.rs flag names)
 static void usage() {
     std::fprintf(stderr,
-                 "sketchy-hip sketch  -o OUT.msh [-i GENOME.fa[.gz] ...] [-s SIZE=1000] [-k K=16] [-e SEED=0]   (paths on stdin without -i)\n"
+                 "sketchy-hip sketch  -o OUT.msh [-i GENOME.fa[.gz] ...] [-s SIZE=1000] [-k K=16] [-e SEED=0] [--counts]   (paths on stdin without -i;\n"
+                 "                    --counts: also write every hash's abundance, Mash's counts32)\n"
                  "sketchy-hip predict -r REF.msh -g GENO.tsv [-i READS.fx[.gz] ...] [-t TOP] [-l LIMIT] [-s] [-c] [-H] [-b BATCH_READS] [-j THREADS] [--timing] [--pin]\n"
                  "                    (without -s: several inputs, one sample each -- the rows of every sample in input order; -l per input; -s: one input)\n"
                  "sketchy-hip shared  -r REF.msh -q QUERY.msh\n"
@@ -873,7 +899,7 @@ int main(int argc, char** argv) {
     const std::map<std::string, std::string> longnames = {{"--input", "-i"}, {"--reference", "-r"}, {"--genotypes", "-g"}, {"--top", "-t"}, {"--limit", "-l"},
                                                           {"--stream", "-s"}, {"--consensus", "-c"}, {"--header", "-H"}, {"--query", "-q"}, {"--params", "-p"},
                                                           {"--device", "-d"}, {"--batch", "-b"}, {"--output", "-o"}, {"--sketch-size", "-s"},
-                                                          {"--kmer-size", "-k"}, {"--seed", "-e"}, {"--threads", "-j"}, {"--timing", "-T"}, {"--pin", "-P"}};
+                                                          {"--kmer-size", "-k"}, {"--seed", "-e"}, {"--threads", "-j"}, {"--timing", "-T"}, {"--pin", "-P"}, {"--counts", "-C"}};
     const bool is_sketch = cmd == "sketch";  // there -s takes a value (sketch size), elsewhere it is --stream
     const bool many_inputs = is_sketch || cmd == "predict";
     for (int i = 2; i < argc; ++i) {
@@ -882,7 +908,7 @@ int main(int argc, char** argv) {
         if (longnames.count(a)) a = longnames.at(a);
         // (predict: a lone "-" is a path -- stdin)
         if (many_inputs && a == "-i") { while (i + 1 < argc && (argv[i + 1][0] != '-' || (!is_sketch && !argv[i + 1][1]))) inputs.push_back(argv[++i]); continue; }
-        if ((!is_sketch && a == "-s") || a == "-c" || a == "-H" || a == "-p" || a == "-T" || a == "-P") flag[a] = true;
+        if ((!is_sketch && a == "-s") || a == "-c" || a == "-H" || a == "-p" || a == "-T" || a == "-P" || a == "-C") flag[a] = true;
         else if (i + 1 < argc) opt[a] = argv[++i];
         else { usage(); return 2; }
     }
@@ -898,7 +924,8 @@ int main(int argc, char** argv) {
             if (!opt.count("-o")) { usage(); return 2; }
             if (inputs.empty()) { std::string line; while (std::getline(std::cin, line)) if (!line.empty()) inputs.push_back(line); }  // src/sketchy.rs:137-146
             app.sketch(inputs, opt["-o"], opt.count("-s") ? (size_t)std::atol(opt["-s"].c_str()) : 1000,
-                       opt.count("-k") ? (uint32_t)std::atoi(opt["-k"].c_str()) : 16u, opt.count("-e") ? std::strtoull(opt["-e"].c_str(), nullptr, 10) : 0ull);
+                       opt.count("-k") ? (uint32_t)std::atoi(opt["-k"].c_str()) : 16u, opt.count("-e") ? std::strtoull(opt["-e"].c_str(), nullptr, 10) : 0ull,
+                       flag["-C"]);
         } else if (cmd == "predict") {
             if (!opt.count("-r") || !opt.count("-g")) { usage(); return 2; }
             if (flag["-s"] && inputs.size() > 1) {

@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import unpack_reads, workload
+from helpers import pack_reads, unpack_reads, workload
 from mshio import write_msh
 from oracle import oracle as orc
 
@@ -75,9 +75,9 @@ def test_check_subcommand(tmp_path):
     assert rc == 1 and "must have the same length" in err
 
 
-def _expected_stream(ref, names, tsv, bases, offsets, top, limit=0, header=False):
+def _expected_stream(ref, names, tsv, bases, offsets, top, limit=0, header=False, k=16, seed=0):
     n = len(offsets) - 1 if not limit else min(limit, len(offsets) - 1)
-    exp = orc.stream(16, 0, ref["ref"].shape[1], ref["ref"], ref["col_len"], bases, offsets[:n + 1], top_k=top)
+    exp = orc.stream(k, seed, ref["ref"].shape[1], ref["ref"], ref["col_len"], bases, offsets[:n + 1], top_k=top)
     geno = {l.split("\t")[0]: l.rstrip("\n").split("\t")[1:] for l in open(tsv).readlines()[1:]}
     lines = ["reads\tsketch_id\tshared_hashes\tmlst\tmeca\tpvl"] if header else []
     for r in range(n):
@@ -111,6 +111,39 @@ def test_predict_stream_rows_fastq_fasta_gz_stdin(gpu, tmp_path):
     assert rc == 0 and out == _expected_stream(ref, names, tsv, bases, offsets, top=1, limit=11)
     rc, out, err = _run("predict", "-r", msh, "-g", tsv, "-i", fq, "-s", "-t", "41")
     assert rc == 1 and "--top exceeds" in err
+
+
+def _write_fastq_and_wrapped_fasta_gz(tmp_path, reads, stem):
+    fq, fa = str(tmp_path / f"{stem}.fq"), str(tmp_path / f"{stem}.fa.gz")
+    with open(fq, "w") as f:
+        for i, r in enumerate(reads):
+            f.write(f"@read{i} desc\n{r.decode()}\n+\n{'I' * len(r)}\n")
+    with gzip.open(fa, "wt") as f:
+        for i, r in enumerate(reads):
+            s = r.decode()
+            f.write(f">read{i}\n" + "\n".join(s[j:j + 70] for j in range(0, len(s), 70)) + "\n")
+    return fq, fa
+
+
+@pytest.mark.gpu
+def test_predict_stream_rows_at_another_k_and_seed(gpu, tmp_path):
+    """The whole production chain at k = 21, seed 42: skx_pack_line -> submit -> the generic-k kernels on 4-bit packed input,
+    in batches of 7 reads (cuts on either nibble parity).  The fixture's reads, then a set with lower case, an N, reads
+    shorter than k and a 9 kb read (split over waves)."""
+    k, seed = 21, 42
+    ref, names, msh, tsv, reads, bases, offsets = _fixture(tmp_path, k=k, seed=seed)
+    g = ref["genome"].tobytes()
+    second = [g[100:601], g[2000:2700].lower(), g[3000:3333] + b"N" + g[3334:3901], g[5000:5020], g[6000:6021], b"ACGT",
+              g[10001:19002], g[20000:20777].lower().replace(b"t", b"u"), g[21000:21300] + b"NNN" + g[21303:21500],
+              g[25000:25555], g[30000:38193]]
+    for stem, rd in (("reads", reads), ("second", second)):
+        b2, o2 = pack_reads(rd)
+        want = _expected_stream(ref, names, tsv, b2, o2, top=3, header=True, k=k, seed=seed)
+        assert any(int(line.split("\t")[2]) > 0 for line in want.split("\n")[1:-1])  # the reads really share hashes
+        for src in _write_fastq_and_wrapped_fasta_gz(tmp_path, rd, stem):
+            rc, out, err = _run("predict", "-r", msh, "-g", tsv, "-i", src, "-t", "3", "-s", "-H", "-b", "7")
+            assert rc == 0, err
+            assert out == want, src
 
 
 @pytest.mark.gpu

@@ -58,6 +58,8 @@ extern "C" {
 #define SKX_MAX_TOP 64u           /* rows ranked per read (sketchy default 1, src/cli.rs:118-119) */
 #define SKX_MAX_SPECIES 64u       /* reference collections resident together in one skx_ref */
 #define SKX_MAX_FEATURES 64u      /* genotype columns of a reference's genotype table (skx_ref_set_genotypes) */
+/* largest entry skx_stream_table_add leaves in the running table (see there): 2^54 - 1 */
+#define SKX_MAX_TABLE_SUM ((1ull << 54) - 1)
 
 typedef struct skx_ref skx_ref;
 typedef struct skx_stream skx_stream;
@@ -202,7 +204,8 @@ int skx_stream_create(skx_stream **out, const skx_ref *ref, uint32_t top_k, uint
  * Outputs are optional (NULL to skip), caller-allocated host arrays:
  *   topk_idx [n_reads][n_species][top_k]  genome indices (within the species) after that read, order =
  *                                         (cumulative sum desc, index asc); n_species = 1 for skx_ref_create
- *   topk_sum [n_reads][n_species][top_k]  the cumulative sums of those genomes after that read
+ *   topk_sum [n_reads][n_species][top_k]  the cumulative sums of those genomes after that read (exact while every entry of the
+ *                                         table is below 2^55 - 1: skx_stream_table_add)
  *   per_read_shared [n_reads][n_genomes]  this read's shared-hash count per genome (parity/debug)
  *   sketches [n_reads][s], sketch_len [n_reads]  the read's bottom-s sketch, ascending (parity/debug)
  * Synchronous: on return the running table includes these reads.
@@ -298,7 +301,13 @@ int skx_stream_drain(skx_stream *st);
 int skx_stream_bind_consensus(skx_stream *st, uint32_t *codes_out);
 /* running sum-of-shared-hashes table, u64[n_genomes] (host) */
 int skx_stream_table(skx_stream *st, uint64_t *cum);
-/* cum[g] += add[g]: resume from a checkpoint, or offset a shard by the totals of earlier shards */
+/*
+ * cum[g] += add[g]: resume from a checkpoint, or offset a shard by the totals of earlier shards.
+ * The table is u64, but rows (topk_idx, topk_sum, skx_stream_rank) and table are exact only while every entry is below 2^55 - 1:
+ * for 2 <= top_k <= 16 the ranking orders genomes by a 64-bit key that holds sum + 1 in 55 bits.  So this call refuses
+ * (SKX_ERR_INVALID, table and stream left as they were) any add that would take an entry above SKX_MAX_TABLE_SUM = 2^54 - 1.  The
+ * 2^54 in between is more than a stream can add: at s = 10 000 shared hashes per read it is 1.8e12 reads.
+ */
 int skx_stream_table_add(skx_stream *st, const uint64_t *add);
 /* zero the table and the read counter */
 int skx_stream_reset(skx_stream *st);
@@ -402,7 +411,8 @@ int skx_comm_unique_id(uint8_t id[SKX_COMM_ID_BYTES]);                 /* rank 0
 int skx_comm_create(skx_comm **out, int device, int rank, int n_ranks, const uint8_t id[SKX_COMM_ID_BYTES]);
 /* ranks of the communicator as RCCL reports them (ncclCommCount) */
 int skx_comm_n_ranks(const skx_comm *comm, int *n_ranks);
-/* in-place sum of the running tables of all ranks' streams (u64, exact) */
+/* in-place sum of the running tables of all ranks' streams (u64, exact); keeping the sum over ranks of every entry below 2^55 - 1
+ * (see skx_stream_table_add) is the caller's: nothing is checked here */
 int skx_stream_allreduce(skx_stream *st, skx_comm *comm);
 void skx_comm_destroy(skx_comm *comm);
 

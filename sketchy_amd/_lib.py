@@ -19,6 +19,7 @@ MAX_K = 32
 MAX_TOP = 64
 MAX_SPECIES = 64
 MAX_FEATURES = 64
+MAX_TABLE_SUM = (1 << 54) - 1
 
 # every symbol include/sketchy_hip.h declares: (name, restype, argtypes)
 _vp, _u32, _u64, _i, _sz = C.c_void_p, C.c_uint32, C.c_uint64, C.c_int, C.c_size_t

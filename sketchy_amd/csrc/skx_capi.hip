@@ -3706,6 +3706,16 @@ SKX_API int skx_stream_table_add(skx_stream* st, const uint64_t* add) {
     SKXCHK(use_device(st->device));
     SKXCHK(flush_pending(st));
     const u32 n = st->ref->n_genomes;
+    // the top-k key holds sum + 1 in 55 bits: no entry may be taken above SKX_MAX_TABLE_SUM, which leaves a stream 2^54 to add.
+    // Checked on the host against the current table before anything is added (not on the timed path); a refused call changes nothing
+    std::vector<u64> cur(n);
+    skx::launch_gather_table(st->hs2, st->d_cum, st->d_tab_tmp, n, st->ref->d_real2pad);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(cur.data(), st->d_tab_tmp, (size_t)n * 8, hipMemcpyDeviceToHost, st->hs2));
+    HIPCHK(hipStreamSynchronize(st->hs2));
+    for (u32 g = 0; g < n; ++g)
+        if (cur[g] > SKX_MAX_TABLE_SUM || add[g] > SKX_MAX_TABLE_SUM - cur[g])  // (no u64 wrap-around: compared before the sum is formed)
+            return fail(SKX_ERR_INVALID, "skx_stream_table_add: genome %u would hold more than 2^54 - 1 = 18014398509481983", g);
     HIPCHK(hipMemcpyAsync(st->d_tab_tmp, add, (size_t)n * 8, hipMemcpyHostToDevice, st->hs2));
     skx::launch_add_table(st->hs2, st->d_cum, st->d_tab_tmp, n, st->ref->d_real2pad);
     st->fresh_table = false;

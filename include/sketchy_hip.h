@@ -22,6 +22,8 @@
  *   skx_rank_sketches      <- the tail of Sketchy::_shared_hashes (src/sketchy.rs:304-312): shared hashes against every
  *                             genome, stable sort, first `top` rows -- for many pooled sketches in one call
  *   skx_predict_groups     <- all of Sketchy::_shared_hashes (src/sketchy.rs:281-315) for many samples: pool, count, rank
+ *   skx_stream_bind_changes / skx_changes_rows <- no counterpart: the reference prints every read's rows (:348-349, :391-399); these
+ *                             report only the reads at which what it would print (indices or consensus) differs from the read before
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
  *   skx_sketch_groups      <- finch SketchScheme::{process x many, to_vec}: ONE sketcher fed several records -- all reads of an
  *                             offline `predict` (src/sketchy.rs:291-302), all contigs of a genome file in `sketch` (:473-478)
@@ -299,6 +301,36 @@ int skx_stream_drain(skx_stream *st);
  * push / submit: streams that never bind pay nothing.
  */
 int skx_stream_bind_consensus(skx_stream *st, uint32_t *codes_out);
+/*
+ * Change points of a batch: only the reads whose call differs from the previous read's, as a short event list.  (The reference prints
+ * `top` lines after EVERY read, src/sketchy.rs:348-349, :391-399; nearly all of them repeat the read before.)
+ * The CALL of read r of a batch is its ranked index row topk_idx[r] (n_species x top_k; sums are no part of it: they move with nearly
+ * every read) or, in codes mode (ev_codes != NULL), its consensus codes [n_species][n_features] (skx_ref_set_genotypes: meaning, tie rule).
+ * Read r is a change point iff r == 0 or call(r) != call(r - 1) in any element; the events of a batch are its change points in
+ * ascending order.  STATELESS PER BATCH: read 0 of every batch is an event and nothing is compared across batches on the device -- the
+ * rankings of enqueued batches run side by side, and a carried "last row" would make every batch wait for the end of the one before.
+ * A caller chaining batches compares the first event of a batch with the last call it kept: one row compare on the host.
+ * Binds, for the NEXT batch handed to skx_stream_push, _push_device, _enqueue_device or _submit (ONE-SHOT, consumed by that call
+ * whether it succeeds or fails, exactly like skx_stream_bind_consensus):
+ *   n_events [1]                          change points of the batch, NOT capped: n_events > cap says the list is truncated (the
+ *                                         batch's full rows are still there if they were asked for)
+ *   ev_read  [cap]                        batch-local read ordinals, ascending
+ *   ev_idx   [cap][n_species][top_k]      optional: topk_idx of those reads
+ *   ev_sum   [cap][n_species][top_k]      optional: topk_sum of those reads
+ *   ev_codes [cap][n_species][n_features] optional: their consensus codes; non-NULL selects codes mode
+ * The first min(n_events, cap) entries are written, nothing else is touched.  The arrays are the kind of memory the entry point's other
+ * outputs are (host / device / page-locked host) and valid whenever that call's rows are.  An empty batch gives n_events = 0.
+ * Codes mode works with or without a consensus output bound for the same batch; the vote goes to the scratch the consensus binding uses.
+ * With a binding, skx_stream_push and skx_stream_submit may be given NULL for topk_idx and topk_sum: then only events travel back.
+ * A bound batch call fails with SKX_ERR_INVALID, before any device work and with the binding consumed, when the stream has top_k == 0,
+ * when a _device entry point is given d_topk_idx == NULL (as for consensus), or in codes mode without a genotype table.
+ * cap == 0, a NULL stream, NULL n_events or ev_read: SKX_ERR_INVALID here.
+ * Found on the device behind the ranking (same queue): a flag per read, an exclusive scan, a gather.  Scratch -- a flag and
+ * a position per read, the event arrays of pushes and submits -- is allocated by the first bound batch; a stream that never binds
+ * launches nothing and allocates nothing for this, and its rows and table are what they were.
+ */
+int skx_stream_bind_changes(skx_stream *st, uint32_t cap, uint32_t *n_events, uint32_t *ev_read, uint32_t *ev_idx, uint64_t *ev_sum,
+                            uint32_t *ev_codes);
 /* running sum-of-shared-hashes table, u64[n_genomes] (host) */
 int skx_stream_table(skx_stream *st, uint64_t *cum);
 /*
@@ -404,6 +436,14 @@ int skx_predict_groups(const skx_ref *ref, const uint8_t *bases, const uint64_t 
  * Errors (all found before any device work): NULL argument, top_k outside 1..SKX_MAX_TOP, no genotype table on the reference, an
  * index >= its species' genome count: SKX_ERR_INVALID.  n_rows == 0: SKX_OK, nothing is touched. */
 int skx_consensus_rows(const skx_ref *ref, const uint32_t *idx, uint64_t n_rows, uint32_t top_k, uint32_t *codes_out);
+
+/* The same operator alone on rows the caller holds (host): the change points of n_rows rows of `width` u32 each, row 0 included.
+ * ev_row [cap] receives the first min(n_events, cap) of them (row indices, ascending; nothing past them is touched), *n_events their
+ * number, not capped.  Works in chunks: at most 64 MiB of rows are on the device at a time; a chunk's first row is compared with the
+ * previous chunk's last row on the host.  width outside 1..4096 (SKX_MAX_SPECIES x SKX_MAX_TOP) or a NULL argument: SKX_ERR_INVALID
+ * before the device is touched.  n_rows == 0: SKX_OK, n_events = 0. */
+int skx_changes_rows(int device, const uint32_t *rows, uint64_t n_rows, uint32_t width, uint64_t cap, uint64_t *n_events,
+                     uint64_t *ev_row);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------- */
 #define SKX_COMM_ID_BYTES 128

@@ -274,8 +274,22 @@ class SumOfSharedHashes:
         """Bind a consensus output (pointer / address; [n_reads, n_species, F] uint32) for the NEXT batch call, which consumes it."""
         _lib.check(_lib.load().skx_stream_bind_consensus(self._h, codes_out))
 
-    def push(self, bases, offsets, want_shared=False, want_sketches=False, want_consensus=False):
-        """Consume a packed batch; returns dict(topk_idx, topk_sum[, shared, sketches, sketch_len, consensus]).  Rows are
+    def bind_changes(self, cap, n_events, ev_read, ev_idx=None, ev_sum=None, ev_codes=None):
+        """Bind an event list (pointers / addresses; skx_stream_bind_changes) for the NEXT batch call, which consumes it: n_events [1],
+        ev_read [cap], ev_idx / ev_sum [cap, n_species, top], ev_codes [cap, n_species, F] (not None: codes mode)."""
+        _lib.check(_lib.load().skx_stream_bind_changes(self._h, cap, n_events, ev_read, ev_idx, ev_sum, ev_codes))
+
+    def _bind(self, consensus, changes):
+        if consensus is not None:
+            self.bind_consensus(consensus)
+        if changes is not None:
+            self.bind_changes(*changes)
+
+    def push(self, bases, offsets, want_shared=False, want_sketches=False, want_consensus=False, want_changes=None, changes_codes=False):
+        """Consume a packed batch; returns dict(topk_idx, topk_sum[, shared, sketches, sketch_len, consensus, changes]).
+        want_changes=cap: also the batch's change points -- the reads whose index row (changes_codes: whose consensus codes) differs
+        from the previous read's, read 0 always among them -- as out["changes"] = dict(n, read, idx, sum[, codes]): n their number
+        (not capped), the arrays the first min(n, cap) of them.  Rows are
         [n_reads, top] for a single reference and [n_reads, n_species, top] (genome indices local to the species)
         for a multi-species one; shared / table() hold the species one after the other.  want_consensus: the consensus codes of
         every read's rows, [n_reads, F] / [n_reads, n_species, F] (the reference needs a genotype table)."""
@@ -295,23 +309,33 @@ class SumOfSharedHashes:
         if want_consensus:
             cons = np.zeros(shape[:-1] + (self.ref.n_features,), np.uint32)
             self.bind_consensus(_p(cons))
+        if want_changes is not None:
+            cap = int(want_changes)
+            ev_n, ev_read = np.zeros(1, np.uint32), np.zeros(cap, np.uint32)
+            ev_idx, ev_sum = np.zeros((cap,) + shape[1:], np.uint32), np.zeros((cap,) + shape[1:], np.uint64)
+            ev_codes = np.zeros((cap,) + shape[1:-1] + (self.ref.n_features,), np.uint32) if changes_codes else None
+            self.bind_changes(cap, _p(ev_n), _p(ev_read), _p(ev_idx), _p(ev_sum), _p(ev_codes))
         _lib.check(L.skx_stream_push(self._h, _p(b), _p(offsets), n, _p(ti), _p(ts), _p(sh), _p(sk), _p(sl)))
         out.update(topk_idx=ti, topk_sum=ts, shared=sh, sketches=sk, sketch_len=sl)
         if want_consensus:
             out["consensus"] = cons
+        if want_changes is not None:
+            m = min(int(ev_n[0]), cap)
+            out["changes"] = dict(n=int(ev_n[0]), read=ev_read[:m], idx=ev_idx[:m], sum=ev_sum[:m])
+            if changes_codes:
+                out["changes"]["codes"] = ev_codes[:m]
         return out
 
-    def push_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None):
-        """consensus: device pointer for the batch's consensus codes, bound right before the call (needs d_topk_idx)"""
-        if consensus is not None:
-            self.bind_consensus(consensus)
+    def push_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None, changes=None):
+        """consensus: device pointer for the batch's consensus codes, bound right before the call (needs d_topk_idx);
+        changes: (cap, n_events, ev_read[, ev_idx, ev_sum, ev_codes]) device pointers of an event list (bind_changes), likewise"""
+        self._bind(consensus, changes)
         _lib.check(_lib.load().skx_stream_push_device(self._h, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum))
 
-    def enqueue_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None):
+    def enqueue_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None, changes=None):
         """push_device with the host wait of batch i overlapped by the sketch of batch i + 1: the passes (and any
         error) of a batch are queued by the NEXT enqueue / flush / sync.  Same rows, same table."""
-        if consensus is not None:
-            self.bind_consensus(consensus)
+        self._bind(consensus, changes)
         _lib.check(_lib.load().skx_stream_enqueue_device(self._h, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum))
 
     def flush(self):
@@ -324,12 +348,12 @@ class SumOfSharedHashes:
     def sync(self):
         _lib.check(_lib.load().skx_stream_sync(self._h))
 
-    def submit(self, h_bases, h_offsets, n_reads, h_topk_idx=None, h_topk_sum=None, consensus=None) -> int:
+    def submit(self, h_bases, h_offsets, n_reads, h_topk_idx=None, h_topk_sum=None, consensus=None, changes=None) -> int:
         """Queue a batch held in page-locked host memory (HostBuffer pointers / addresses); returns its ticket.  The
         copy overlaps the previous batch's kernels; rows are valid after wait(ticket) or drain().  consensus: page-locked
-        pointer for the batch's consensus codes, bound right before the call; the row pointers may then be None."""
-        if consensus is not None:
-            self.bind_consensus(consensus)
+        pointer for the batch's consensus codes, bound right before the call; the row pointers may then be None.  changes:
+        (cap, n_events, ev_read[, ev_idx, ev_sum, ev_codes]) page-locked pointers of an event list (bind_changes), likewise."""
+        self._bind(consensus, changes)
         t = C.c_uint64(0)
         _lib.check(_lib.load().skx_stream_submit(self._h, h_bases, h_offsets, n_reads, h_topk_idx, h_topk_sum, C.byref(t)))
         return t.value
@@ -436,6 +460,21 @@ class Comm:
         if getattr(self, "_h", None):
             _lib.load().skx_comm_destroy(self._h)
             self._h = None
+
+
+def changes_rows(rows, cap=None, device=0):
+    """Change points of rows held on the host (skx_changes_rows): rows [n, ...] uint32, compared row by row over all trailing axes
+    (1..4096 values per row).  Returns (n_events, ev_row): the number of rows that differ from the row before them, row 0 included
+    -- not capped --, and the first min(n_events, cap) of their indices (uint64); cap None: room for all."""
+    rows = np.ascontiguousarray(rows, np.uint32)
+    n = rows.shape[0] if rows.ndim else 0
+    width = int(np.prod(rows.shape[1:], dtype=np.int64)) if rows.ndim > 1 else 1
+    cap = n if cap is None else int(cap)
+    ev = np.zeros(max(cap, 1), np.uint64)
+    n_ev = C.c_uint64(0)
+    src = rows if rows.size else np.zeros(1, np.uint32)
+    _lib.check(_lib.load().skx_changes_rows(device, _p(src), n, width, cap, C.byref(n_ev), _p(ev)))
+    return n_ev.value, ev[:min(n_ev.value, cap)]
 
 
 def sketch_reads(bases, offsets, k=16, seed=0, s=1000, device=0):

@@ -919,6 +919,16 @@ struct TimedSpan { int stage; hipEvent_t a, b; };
 // passes.  skx_stream_push* run both halves in one call; skx_stream_enqueue_device runs the front half of batch i + 1
 // BEFORE the back half of batch i, so the sketch stream never waits for the host between two batches.
 static const int kGroupMax = skx::kPairBaseMax + 1;  // batches that may share one pass (option stream_coalesce)
+// Event list of a batch (skx_stream_bind_changes): where its change points go.  In skx_stream::bound_chg the caller's arrays (whatever
+// memory the entry point takes); in a PendingBatch / SubPass DEVICE arrays, filled behind the batch's last pass.  cap == 0: none.
+struct ChangeOut {
+    u32 cap = 0;
+    u32 n_batch = 0;  // reads of the batch: the sub-pass that ends there queues the scan and the gather
+    u32 *n_events = nullptr, *ev_read = nullptr, *ev_idx = nullptr;
+    u64* ev_sum = nullptr;
+    u32* ev_codes = nullptr;
+    bool codes = false;  // the call of a read is its consensus codes, not its index row
+};
 struct PendingBatch {
     bool valid = false;
     int side = 0;  // which copy of the sketch buffers holds it
@@ -945,6 +955,7 @@ struct PendingBatch {
     u32* h_sketch_len = nullptr;
     void* slot = nullptr;      // skx_stream::Staged of a host-fed batch: its rows travel to the host behind the ranking
     u32* d_cons = nullptr;     // [n_reads][n_species][n_features] consensus codes of its rows (skx_stream_bind_consensus) or NULL
+    ChangeOut chg;             // its event list (skx_stream_bind_changes)
 };
 
 // The HIP streams of the pipeline, ONE set per device shared by every skx_stream on it.  Measured (tools/diag_second_stream.py,
@@ -982,6 +993,7 @@ struct SubPass {
     int side = 0;
     void* slot = nullptr;         // host-fed batches: the staging slot whose rows go back to the host behind the ranking
     u32* d_cons = nullptr;        // consensus codes of the BATCH's rows (row 0 = the batch's first read) or NULL
+    ChangeOut chg;                // the BATCH's event list: flags for [ra, rb) here, scan + gather when rb ends the batch
 };
 static const int kSides = kGroupMax + 1;  // copies of the per-batch sketch outputs: the enqueued batches waiting for their shared pass + the one being sketched
                                           // (a stream uses stream_coalesce + 1 of them, allocated at first use)
@@ -1183,6 +1195,9 @@ struct skx_stream {
         u64 *d_cand_sum = nullptr;
         u32 *d_cand_idx = nullptr;
         u64 *d_cum_sink = nullptr;  // [n_pad] the table the chain's prefix kernels write (round 5: the real one comes from the pass's gains)
+        // change points (skx_stream_bind_changes; allocated by the first bound batch the lane ranks): one flag and one position per read
+        // of a batch, the scan's block totals, and -- codes mode of a _device entry point without a consensus output -- the codes voted on
+        u32 *d_chg_flag = nullptr, *d_chg_pos = nullptr, *d_chg_bsum = nullptr, *d_chg_codes = nullptr;
         hipEvent_t ev_cum = nullptr;   // its chain's chunk_prefix is done: the table the NEXT batch starts from is complete
         hipEvent_t ev_done = nullptr;  // its chain is done
         bool ready = false;
@@ -1203,6 +1218,10 @@ struct skx_stream {
     // skx_stream_push writes them to ([max_reads][n_species][n_features], allocated by the first such push)
     u32* bound_cons = nullptr;
     u32* d_cons = nullptr;
+    // event list (skx_stream_bind_changes): the arrays bound for the next batch call, and the device copy a bound skx_stream_push
+    // gathers into (d_ev: {n_events, ev_read, ev_idx, ev_sum, ev_codes} for d_ev.cap entries; grows with the caps asked for)
+    ChangeOut bound_chg;
+    ChangeOut d_ev;
     u64* d_tab_tmp = nullptr;   // [n_genomes] staging of skx_stream_table / skx_stream_table_add
     u32* d_rank_idx = nullptr;  // [n_species][top] outputs of skx_stream_rank
     u64* d_rank_sum = nullptr;
@@ -1249,6 +1268,9 @@ struct skx_stream {
         u64* out_sum = nullptr;
         u32* out_cons = nullptr;    // consensus codes of the batch (page-locked host) or NULL; d_cons: the slot's device copy, allocated
         u32* d_cons = nullptr;      // for every slot by the first bound submit
+        ChangeOut out_chg;          // event list of the batch (the caller's page-locked arrays) or cap == 0; d_ev: the slot's device copy
+        ChangeOut d_ev;             // (allocated by the slot's first bound submit, grows with the caps asked for); h_ev_n: page-locked, the
+        u32* h_ev_n = nullptr;      // batch's n_events on its way back -- the host copies min(n_events, cap) entries once it is there
         u32* d_rows_idx = nullptr;  // the slot's own device rows (batches may share a pass: each needs its rows until they are copied out)
         u64* d_rows_sum = nullptr;
         uint8_t* d_bases = nullptr;
@@ -1286,7 +1308,7 @@ static void stream_free(skx_stream* st) {
     void* ptrs[] = {st->d_bases, st->d_offsets, st->d_pair_h[0], st->d_pair_h[1],
                     st->d_q[0], st->d_q[1], st->d_pair_r[0], st->d_pair_r[1], st->d_pair_q[0], st->d_pair_q[1],
                     st->d_poff_pass[0], st->d_poff_pass[1], st->d_poff_pass[2], st->d_pair_r[2], st->d_nq[0], st->d_nq[1], st->d_win[0], st->d_win[1], st->d_m, st->d_mint, st->d_mq[0], st->d_mq[1],
-                    st->d_topk_idx, st->d_topk_sum, st->d_cons, st->d_tab_tmp, st->d_rank_idx, st->d_rank_sum, st->d_bsum, st->d_grp_any[0],
+                    st->d_topk_idx, st->d_topk_sum, st->d_cons, st->d_ev.n_events, st->d_ev.ev_read, st->d_ev.ev_idx, st->d_ev.ev_sum, st->d_ev.ev_codes, st->d_tab_tmp, st->d_rank_idx, st->d_rank_sum, st->d_bsum, st->d_grp_any[0],
                     st->d_grp_any[1], st->d_hbuf, st->d_wb[0], st->d_wb[1], st->d_rowany[0], st->d_rowany[1], st->d_mqext,
                     st->d_qd, st->d_qrow, st->d_sslot, st->d_qinfo, st->d_qloc, st->d_cls_bsum, st->d_nd_hs,
                     st->d_rowcnt, st->d_gain, st->d_gain_s, st->d_candslot, st->d_candmask, st->d_lrow, st->d_nlrow, st->d_gain_l, st->d_cbase, st->d_cwl, st->d_ncwl, st->d_cw, st->d_cbad, st->d_nqc, st->d_spc_g0, st->d_spc_grp, st->d_inb, st->d_hit, st->d_hist, st->d_nprow, st->d_pcw, st->d_ms[0], st->d_ms[1], st->d_mdirty_s};
@@ -1317,6 +1339,8 @@ static void stream_free(skx_stream* st) {
     (void)hipFree(st->d_btot);
     for (auto& sl : st->slot) {
         (void)hipFree(sl.d_bases); (void)hipFree(sl.d_offsets); (void)hipFree(sl.d_rows_idx); (void)hipFree(sl.d_rows_sum); (void)hipFree(sl.d_cons);
+        (void)hipFree(sl.d_ev.n_events); (void)hipFree(sl.d_ev.ev_read); (void)hipFree(sl.d_ev.ev_idx); (void)hipFree(sl.d_ev.ev_sum); (void)hipFree(sl.d_ev.ev_codes);
+        if (sl.h_ev_n) (void)hipHostFree(sl.h_ev_n);
         if (sl.h_offsets) (void)hipHostFree(sl.h_offsets);
         if (sl.ev_copy) (void)hipEventDestroy(sl.ev_copy);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
@@ -1464,7 +1488,8 @@ static hipError_t alloc_lane_parts(skx_stream* st, int i) {
 static void free_lane(skx_stream* st, int i) {
     skx_stream::RankLane& L = st->lane[i];
     void* ptrs[] = {L.d_inc, L.d_rel, L.d_live, L.d_has, L.d_lead_seg, L.d_live_ctr, L.d_csum, L.d_csum_raw, L.d_leader, L.d_lead_val,
-                    L.d_lpart_sum, L.d_lpart_idx, L.d_gmax, L.d_cand_sum, L.d_cand_idx, L.d_cum_sink};
+                    L.d_lpart_sum, L.d_lpart_idx, L.d_gmax, L.d_cand_sum, L.d_cand_idx, L.d_cum_sink,
+                    L.d_chg_flag, L.d_chg_pos, L.d_chg_bsum, L.d_chg_codes};
     for (void* q : ptrs) (void)hipFree(q);
     if (L.ev_cum) (void)hipEventDestroy(L.ev_cum);
     if (L.ev_done) (void)hipEventDestroy(L.ev_done);
@@ -2643,6 +2668,34 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
         if (sb.d_cons)  // the vote over the rows this sub-pass has just finished, behind the last kernel that writes them
             skx::launch_consensus_rows(ls, d_topk_idx, out_r0, n_reads, n_sp, st->top_k, ref->d_sp_g0, ref->d_codes, ref->n_features,
                                        sb.d_cons, n_pad);
+        if (sb.chg.cap) {
+            // change points of the batch: flags for the reads this sub-pass has just finished, behind the last kernel that writes their
+            // rows (or codes); the scan and the gather behind the batch's last sub-pass.  Row ra - 1 of a batch cut into passes was
+            // written by the pass before: passes of one batch are passes of their own (n_sub == 1) and run on lane 0 one behind the
+            // other, and the batches of a shared pass begin at read 0, which compares with nothing.
+            if (sb.ra != 0 && li != 0) return fail(SKX_ERR_HIP, "internal: a later pass of a batch left lane 0");
+            if (!L.d_chg_flag) {
+                HIPCHK(hipMalloc(&L.d_chg_flag, (size_t)st->max_reads * 4));
+                HIPCHK(hipMalloc(&L.d_chg_pos, (size_t)st->max_reads * 4));
+                HIPCHK(hipMalloc(&L.d_chg_bsum, ((size_t)st->max_reads / 1024 + 1) * 4));
+            }
+            const u32 w_idx = n_sp * st->top_k, w_codes = n_sp * ref->n_features;
+            u32* d_codes = nullptr;
+            if (sb.chg.codes) {
+                d_codes = sb.d_cons;
+                if (!d_codes) {  // (no consensus output travels with the batch: the vote goes to the lane's own scratch)
+                    if (!L.d_chg_codes) HIPCHK(hipMalloc(&L.d_chg_codes, (size_t)st->max_reads * w_codes * 4));
+                    d_codes = L.d_chg_codes;
+                    skx::launch_consensus_rows(ls, d_topk_idx, out_r0, n_reads, n_sp, st->top_k, ref->d_sp_g0, ref->d_codes, ref->n_features,
+                                               d_codes, n_pad);
+                }
+            }
+            skx::launch_change_flags(ls, d_codes ? d_codes : d_topk_idx, d_codes ? w_codes : w_idx, sb.ra, sb.rb, L.d_chg_flag);
+            if (sb.rb == sb.chg.n_batch)
+                skx::launch_change_events(ls, L.d_chg_flag, L.d_chg_pos, L.d_chg_bsum, sb.chg.n_batch, sb.chg.cap, sb.chg.n_events,
+                                          sb.chg.ev_read, sb.chg.ev_idx ? d_topk_idx : nullptr, sb.chg.ev_sum ? d_topk_sum : nullptr, w_idx,
+                                          sb.chg.ev_idx, sb.chg.ev_sum, sb.chg.ev_codes ? d_codes : nullptr, w_codes, sb.chg.ev_codes);
+        }
     }
     if (sb.d_shared)
         skx::launch_shared_debug(ls, d_pair_q + sb.p_off, sub_poff, sub_base, 0, n_reads, d_mq, nq_rows, ref->n_genomes, ref->d_real2pad, sb.d_shared, 0);
@@ -2680,9 +2733,11 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
 
 static int run_pass(skx_stream* st, u32 ra, u32 rb, u32 p_base, u32 P, u32* d_topk_idx, u64* d_topk_sum,
                     u32* d_shared /* [rb-ra][n_genomes] or NULL */, bool update_table, bool inserted = false, u32 q_rows = 0xFFFFFFFFu,
-                    void* slot = nullptr, u32* d_counts = nullptr /* [rb-ra][n_pad] or NULL */, u32* d_cons = nullptr) {
+                    void* slot = nullptr, u32* d_counts = nullptr /* [rb-ra][n_pad] or NULL */, u32* d_cons = nullptr,
+                    const ChangeOut* chg = nullptr) {
     SubPass sb;
     sb.slot = slot; sb.d_cons = d_cons;
+    if (chg) sb.chg = *chg;
     sb.ra = ra; sb.rb = rb; sb.p_off = 0; sb.P = P; sb.p_base = p_base; sb.d_topk_idx = d_topk_idx; sb.d_topk_sum = d_topk_sum;
     sb.d_shared = d_shared; sb.d_counts = d_counts; sb.side = st->side;
     sb.d_poff = st->d_poff_pass[st->pslot];  // (inserted passes: the front half's copy; else run_pass_multi fills the slot itself)
@@ -3071,12 +3126,15 @@ static int batch_back(skx_stream* st, PendingBatch& pb, PendingBatch* younger) {
     if (inserted && (st->buf != pb.spec_set || st->pslot != pb.spec_slot)) return fail(SKX_ERR_HIP, "internal: buffer sets out of step");
     u32* d_shared = nullptr;
     auto one_pass = [&](u32 ra, u32 rb, u32 p_base, u32 P) -> int {
+#ifdef SKX_EXPERIMENTS
+        if (skx::knob("SKX_DEBUG_PASS")) fprintf(stderr, "[skx pass cut] reads %u %u\n", ra, rb);  // (tests: which reads begin a pass)
+#endif
         if (pb.h_shared) {
             if (d_shared) { (void)hipFree(d_shared); d_shared = nullptr; }
             HIPCHK(hipMalloc(&d_shared, (size_t)(rb - ra) * ref->n_genomes * 4));
         }
         SKXCHK(run_pass(st, ra, rb, p_base, P, pb.d_topk_idx, pb.d_topk_sum, d_shared, true, inserted, inserted ? q_rows : 0xFFFFFFFFu,
-                        rb == n_reads ? pb.slot : nullptr, nullptr, pb.d_cons));
+                        rb == n_reads ? pb.slot : nullptr, nullptr, pb.d_cons, &pb.chg));
         inserted = false;
         st->last_passes += 1;
         if (pb.h_shared) {
@@ -3183,7 +3241,7 @@ static int batch_back_group(skx_stream* st, PendingBatch* g, int n, PendingBatch
         subs[i].d_topk_idx = g[i].d_topk_idx; subs[i].d_topk_sum = g[i].d_topk_sum;
         subs[i].p_off = p_off; subs[i].P = P[i];
         subs[i].d_poff = st->d_poff_pass[g[0].spec_slot] + (size_t)i * ((size_t)st->rpass + 2);
-        subs[i].slot = g[i].slot; subs[i].d_cons = g[i].d_cons;
+        subs[i].slot = g[i].slot; subs[i].d_cons = g[i].d_cons; subs[i].chg = g[i].chg;
         p_off += P[i];
     }
     st->last_pairs = pairs; st->last_passes = 1; st->shared_passes += 1;
@@ -3228,13 +3286,15 @@ static int flush_pending(skx_stream* st) {
 // sketch + score + rank a batch already resident on the device, both halves (synchronous entry points).
 // h_shared / h_sketches / h_sketch_len: optional HOST outputs (parity/debug).
 static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_offsets, u32 n_reads, u64 n_bases, u32* d_topk_idx,
-                         u64* d_topk_sum, u32* h_shared, u64* h_sketches, u32* h_sketch_len, u32* d_cons = nullptr) {
+                         u64* d_topk_sum, u32* h_shared, u64* h_sketches, u32* h_sketch_len, u32* d_cons = nullptr,
+                         const ChangeOut* chg = nullptr) {
     if (n_reads == 0) return SKX_OK;
     SKXCHK(flush_pending(st));
     PendingBatch pb;
     pb.d_bases = d_bases; pb.d_offsets = d_offsets; pb.n_reads = n_reads; pb.n_bases = n_bases;
     pb.d_topk_idx = d_topk_idx; pb.d_topk_sum = d_topk_sum;
     pb.h_shared = h_shared; pb.h_sketches = h_sketches; pb.h_sketch_len = h_sketch_len; pb.d_cons = d_cons;
+    if (chg) { pb.chg = *chg; pb.chg.n_batch = n_reads; }
     SKXCHK(batch_front(st, pb));
     st->tail_pass = true;  // (a synchronous push: the batch's passes have the chip to themselves)
     const int rc = batch_back(st, pb, nullptr);
@@ -3246,9 +3306,10 @@ static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_of
 // next group runs the shared back half of the one before it, behind its own front half.  Errors of a batch surface here up to
 // stream_coalesce calls late (or in the flush); the batches enqueued after it up to that call are dropped too.
 static int enqueue_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_offsets, u32 n_reads, u64 n_bases, u32* d_topk_idx,
-                         u64* d_topk_sum, void* slot, u32* d_cons) {
+                         u64* d_topk_sum, void* slot, u32* d_cons, const ChangeOut* chg = nullptr) {
     PendingBatch nw;
     nw.d_cons = d_cons;
+    if (chg) { nw.chg = *chg; nw.chg.n_batch = n_reads; }
     nw.d_bases = d_bases; nw.d_offsets = d_offsets; nw.n_reads = n_reads; nw.n_bases = n_bases;
     nw.d_topk_idx = d_topk_idx; nw.d_topk_sum = d_topk_sum; nw.slot = slot;
     nw.pairable = st->coalesce >= 2;
@@ -3306,14 +3367,82 @@ SKX_API int skx_stream_bind_consensus(skx_stream* st, uint32_t* codes_out) {
     return SKX_OK;
 }
 
+// ---- event list of a batch (skx_stream_bind_changes): one-shot like the consensus binding, taken by every batch entry point first
+static ChangeOut take_changes(skx_stream* st) {
+    const ChangeOut c = st->bound_chg;
+    st->bound_chg = ChangeOut{};
+    return c;
+}
+static int check_changes(const char* who, const skx_stream* st, const ChangeOut& c, bool device_entry, const void* device_rows) {
+    if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: an event list is bound but the stream was created with top_k=0", who);
+    if (device_entry && !device_rows) return fail(SKX_ERR_INVALID, "%s: an event list is bound but d_topk_idx is NULL", who);
+    if (c.codes && !st->ref->d_codes) return fail(SKX_ERR_INVALID, "%s: an event list of codes is bound but the reference has no genotype table", who);
+    return SKX_OK;
+}
+// device arrays of an event list for `cap` entries (push: the stream's, submit: a slot's).  They grow when a larger cap (or the first
+// list of codes) arrives; the caller has made sure that nothing queued still uses them.
+static int ensure_events(const skx_stream* st, ChangeOut& d, u32 cap, bool want_codes) {
+    if (d.n_events && d.cap >= cap && (!want_codes || d.ev_codes)) return SKX_OK;
+    (void)hipFree(d.n_events); (void)hipFree(d.ev_read); (void)hipFree(d.ev_idx); (void)hipFree(d.ev_sum); (void)hipFree(d.ev_codes);
+    const u32 keep = std::max(cap, d.cap);
+    d = ChangeOut{};
+    const size_t w_idx = (size_t)st->ref->n_species * st->top_k, w_codes = (size_t)st->ref->n_species * st->ref->n_features;
+    HIPCHK(hipMalloc(&d.n_events, 4));
+    HIPCHK(hipMalloc(&d.ev_read, (size_t)keep * 4));
+    HIPCHK(hipMalloc(&d.ev_idx, (size_t)keep * w_idx * 4));
+    HIPCHK(hipMalloc(&d.ev_sum, (size_t)keep * w_idx * 8));
+    if (w_codes) HIPCHK(hipMalloc(&d.ev_codes, (size_t)keep * w_codes * 4));
+    d.cap = keep;
+    return SKX_OK;
+}
+// what the kernels get: the device arrays `d` for the outputs the caller asked for in `want`
+static ChangeOut device_events(const ChangeOut& want, const ChangeOut& d) {
+    ChangeOut c;
+    c.cap = std::min(want.cap, d.cap);
+    c.n_events = d.n_events; c.ev_read = d.ev_read;
+    c.ev_idx = want.ev_idx ? d.ev_idx : nullptr;
+    c.ev_sum = want.ev_sum ? d.ev_sum : nullptr;
+    c.ev_codes = want.ev_codes ? d.ev_codes : nullptr;
+    c.codes = want.codes;
+    return c;
+}
+// the first min(n, cap) entries of the device arrays `d` to the caller's host arrays; nothing past them is touched
+static int deliver_events(const skx_stream* st, const ChangeOut& want, const ChangeOut& d, u32 n) {
+    *want.n_events = n;
+    const size_t m = std::min(n, std::min(want.cap, d.cap));
+    if (m == 0) return SKX_OK;
+    const size_t w_idx = (size_t)st->ref->n_species * st->top_k, w_codes = (size_t)st->ref->n_species * st->ref->n_features;
+    HIPCHK(hipMemcpy(want.ev_read, d.ev_read, m * 4, hipMemcpyDeviceToHost));
+    if (want.ev_idx) HIPCHK(hipMemcpy(want.ev_idx, d.ev_idx, m * w_idx * 4, hipMemcpyDeviceToHost));
+    if (want.ev_sum) HIPCHK(hipMemcpy(want.ev_sum, d.ev_sum, m * w_idx * 8, hipMemcpyDeviceToHost));
+    if (want.ev_codes) HIPCHK(hipMemcpy(want.ev_codes, d.ev_codes, m * w_codes * 4, hipMemcpyDeviceToHost));
+    return SKX_OK;
+}
+
+SKX_API int skx_stream_bind_changes(skx_stream* st, uint32_t cap, uint32_t* n_events, uint32_t* ev_read, uint32_t* ev_idx, uint64_t* ev_sum,
+                                    uint32_t* ev_codes) {
+    if (!st || !n_events || !ev_read) return fail(SKX_ERR_INVALID, "skx_stream_bind_changes: NULL argument");
+    if (cap == 0) return fail(SKX_ERR_INVALID, "skx_stream_bind_changes: cap must be at least 1");
+    ChangeOut c;
+    c.cap = cap; c.n_events = n_events; c.ev_read = ev_read; c.ev_idx = ev_idx; c.ev_sum = reinterpret_cast<u64*>(ev_sum);
+    c.ev_codes = ev_codes; c.codes = ev_codes != nullptr;
+    st->bound_chg = c;
+    return SKX_OK;
+}
+
 SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads,
                             uint32_t* topk_idx, uint64_t* topk_sum, uint32_t* per_read_shared, uint64_t* sketches,
                             uint32_t* sketch_len) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL argument");
     u32* const cons = take_consensus(st);
+    const ChangeOut chg = take_changes(st);
     if (!offsets) return fail(SKX_ERR_INVALID, "NULL argument");
     if (cons) SKXCHK(check_consensus("skx_stream_push", st, false, nullptr));
-    if (n_reads == 0) return SKX_OK;
+    if (chg.cap) SKXCHK(check_changes("skx_stream_push", st, chg, false, nullptr));
+    if (n_reads == 0) {
+        if (chg.cap) *chg.n_events = 0;
+        return SKX_OK;
+    }
     if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
     for (u32 r = 0; r < n_reads; ++r)
         if (offsets[r + 1] < offsets[r]) return fail(SKX_ERR_INVALID, "offsets not monotonic at read %u", r);
@@ -3323,8 +3452,14 @@ SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t
     if (n_bases && !bases) return fail(SKX_ERR_INVALID, "bases is NULL");
     if ((topk_idx || topk_sum) && st->top_k == 0) return fail(SKX_ERR_INVALID, "stream was created with top_k=0");
     SKXCHK(use_device(st->device));
-    if (cons && !st->d_cons) HIPCHK(hipMalloc(&st->d_cons, consensus_bytes(st, st->max_reads)));
+    const bool vote = cons || chg.codes;  // (an event list of codes votes into the same scratch)
+    if (vote && !st->d_cons) HIPCHK(hipMalloc(&st->d_cons, consensus_bytes(st, st->max_reads)));
     SKXCHK(flush_pending(st));
+    ChangeOut d_chg;
+    if (chg.cap) {  // (pushes are synchronous: nothing queued uses the stream's event arrays)
+        SKXCHK(ensure_events(st, st->d_ev, std::min(chg.cap, st->max_reads), chg.codes));
+        d_chg = device_events(chg, st->d_ev);
+    }
     hipStream_t hs = st->hs0;
     // rebase offsets to 0 on the way in (packed input: to the first byte that holds a base of the batch)
     const u64 byte0 = st->packed ? base0 >> 1 : base0, rebase = st->packed ? byte0 * 2 : base0;
@@ -3333,14 +3468,17 @@ SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t
     HIPCHK(hipMemcpyAsync(st->d_offsets, st->h_offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, hs));
     if (n_bases) HIPCHK(hipMemcpyAsync(st->d_bases, bases + byte0, n_bytes, hipMemcpyHostToDevice, hs));
     SKXCHK(process_batch(st, st->d_bases, st->d_offsets, n_reads, n_bases, st->d_topk_idx, st->d_topk_sum,
-                         per_read_shared, reinterpret_cast<u64*>(sketches), sketch_len, cons ? st->d_cons : nullptr));
+                         per_read_shared, reinterpret_cast<u64*>(sketches), sketch_len, vote ? st->d_cons : nullptr, chg.cap ? &d_chg : nullptr));
     SKXCHK(queue_chains(st, true));    // the ranking of the batch's last pass (waits for its candidates)
     HIPCHK(hipStreamSynchronize(hs));  // sketch copies (first stream)
     const size_t rows = (size_t)n_reads * st->ref->n_species * st->top_k;
     if (topk_idx) HIPCHK(hipMemcpyAsync(topk_idx, st->d_topk_idx, rows * 4, hipMemcpyDeviceToHost, st->hs2));
     if (topk_sum) HIPCHK(hipMemcpyAsync(topk_sum, st->d_topk_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
     if (cons) HIPCHK(hipMemcpyAsync(cons, st->d_cons, consensus_bytes(st, n_reads), hipMemcpyDeviceToHost, st->hs2));
+    u32 n_ev = 0;
+    if (chg.cap) HIPCHK(hipMemcpyAsync(&n_ev, st->d_ev.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
     HIPCHK(hipStreamSynchronize(st->hs2));  // the rows are written by the back half
+    if (chg.cap) SKXCHK(deliver_events(st, chg, st->d_ev, n_ev));
     if (st->profiling) collect_spans(st);
     return SKX_OK;
 }
@@ -3358,24 +3496,39 @@ static int check_device_batch(skx_stream* st, const uint8_t* d_bases, const uint
 SKX_API int skx_stream_push_device(skx_stream* st, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
                                    uint64_t n_bases, uint32_t* d_topk_idx, uint64_t* d_topk_sum) {
     u32* const cons = st ? take_consensus(st) : nullptr;
+    const ChangeOut chg = st ? take_changes(st) : ChangeOut{};
     SKXCHK(check_device_batch(st, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum));
     if (cons) SKXCHK(check_consensus("skx_stream_push_device", st, true, d_topk_idx));
+    if (chg.cap) SKXCHK(check_changes("skx_stream_push_device", st, chg, true, d_topk_idx));
     SKXCHK(use_device(st->device));
-    if (n_reads == 0) return flush_pending(st);
+    if (n_reads == 0) {
+        SKXCHK(flush_pending(st));
+        if (chg.cap) HIPCHK(hipMemsetAsync(chg.n_events, 0, 4, st->hs2));
+        return SKX_OK;
+    }
     u32* ti = d_topk_idx ? d_topk_idx : st->d_topk_idx;
     u64* ts = d_topk_sum ? reinterpret_cast<u64*>(d_topk_sum) : st->d_topk_sum;
-    return process_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, nullptr, nullptr, cons);
+    return process_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, nullptr, nullptr, cons,
+                         chg.cap ? &chg : nullptr);
 }
 SKX_API int skx_stream_enqueue_device(skx_stream* st, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
                                       uint64_t n_bases, uint32_t* d_topk_idx, uint64_t* d_topk_sum) {
     u32* const cons = st ? take_consensus(st) : nullptr;
+    const ChangeOut chg = st ? take_changes(st) : ChangeOut{};
     SKXCHK(check_device_batch(st, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum));
     if (cons) SKXCHK(check_consensus("skx_stream_enqueue_device", st, true, d_topk_idx));
-    if (n_reads == 0) return SKX_OK;
+    if (chg.cap) SKXCHK(check_changes("skx_stream_enqueue_device", st, chg, true, d_topk_idx));
+    if (n_reads == 0) {
+        if (chg.cap) {
+            SKXCHK(use_device(st->device));
+            HIPCHK(hipMemsetAsync(chg.n_events, 0, 4, st->hs2));
+        }
+        return SKX_OK;
+    }
     SKXCHK(use_device(st->device));
     u32* ti = d_topk_idx ? d_topk_idx : st->d_topk_idx;
     u64* ts = d_topk_sum ? reinterpret_cast<u64*>(d_topk_sum) : st->d_topk_sum;
-    return enqueue_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, cons);
+    return enqueue_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, cons, chg.cap ? &chg : nullptr);
 }
 SKX_API int skx_stream_flush(skx_stream* st) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
@@ -3392,9 +3545,19 @@ static int staged_rows(skx_stream* st, void* slot) {
     if (sl.out_idx) HIPCHK(hipMemcpyAsync(sl.out_idx, sl.d_rows_idx, rows * 4, hipMemcpyDeviceToHost, st->hs2));
     if (sl.out_sum) HIPCHK(hipMemcpyAsync(sl.out_sum, sl.d_rows_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
     if (sl.out_cons) HIPCHK(hipMemcpyAsync(sl.out_cons, sl.d_cons, consensus_bytes(st, sl.n_reads), hipMemcpyDeviceToHost, st->hs2));
+    if (sl.out_chg.cap) HIPCHK(hipMemcpyAsync(sl.h_ev_n, sl.d_ev.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
     HIPCHK(hipEventRecord(sl.ev_done, st->hs2));
     sl.in_flight = true;
     return SKX_OK;
+}
+// the batch is through (ev_done has been waited for): its events go from the slot's device arrays to the caller's -- n_events is
+// known only now, and nothing past min(n_events, cap) may be written
+static int staged_landed(skx_stream* st, skx_stream::Staged& sl) {
+    sl.in_flight = false;
+    if (!sl.out_chg.cap) return SKX_OK;
+    const ChangeOut want = sl.out_chg;
+    sl.out_chg = ChangeOut{};
+    return deliver_events(st, want, sl.d_ev, *static_cast<volatile u32*>(sl.h_ev_n));
 }
 static void staged_drop(void* slot) {
     if (slot) static_cast<skx_stream::Staged*>(slot)->dropped = true;
@@ -3404,7 +3567,10 @@ static int staged_process(skx_stream* st, skx_stream::Staged& sl) {
     if (!sl.pending) return SKX_OK;
     sl.pending = false;
     HIPCHK(hipStreamWaitEvent(st->hs0, sl.ev_copy, 0));  // the batch must have landed before the sketcher reads it
-    return enqueue_batch(st, sl.d_bases, sl.d_offsets, sl.n_reads, sl.n_bases, sl.d_rows_idx, sl.d_rows_sum, &sl, sl.out_cons ? sl.d_cons : nullptr);
+    ChangeOut d_chg;
+    if (sl.out_chg.cap) d_chg = device_events(sl.out_chg, sl.d_ev);
+    return enqueue_batch(st, sl.d_bases, sl.d_offsets, sl.n_reads, sl.n_bases, sl.d_rows_idx, sl.d_rows_sum, &sl,
+                         (sl.out_cons || sl.out_chg.codes) ? sl.d_cons : nullptr, sl.out_chg.cap ? &d_chg : nullptr);
 }
 // ... until its rows are on the host
 static int staged_finish(skx_stream* st, skx_stream::Staged& sl) {
@@ -3417,15 +3583,17 @@ static int staged_finish(skx_stream* st, skx_stream::Staged& sl) {
         for (int i = 0; i < pc.n_sub; ++i) mine = mine || pc.subs[i].slot == &sl;
         if (mine) { SKXCHK(queue_chains_until(st, st->pc_n - k - 1)); break; }
     }
-    if (sl.in_flight) { HIPCHK(hipEventSynchronize(sl.ev_done)); sl.in_flight = false; }
+    if (sl.in_flight) { HIPCHK(hipEventSynchronize(sl.ev_done)); SKXCHK(staged_landed(st, sl)); }
     return SKX_OK;
 }
 SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads,
                               uint32_t* topk_idx, uint64_t* topk_sum, uint64_t* ticket) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL argument");
     u32* const cons = take_consensus(st);
+    const ChangeOut chg = take_changes(st);
     if (!offsets) return fail(SKX_ERR_INVALID, "NULL argument");
     if (cons) SKXCHK(check_consensus("skx_stream_submit", st, false, nullptr));
+    if (chg.cap) SKXCHK(check_changes("skx_stream_submit", st, chg, false, nullptr));
     if (n_reads == 0) return fail(SKX_ERR_INVALID, "empty batch");
     if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
     for (u32 r = 0; r < n_reads; ++r)
@@ -3464,6 +3632,11 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
     // engine stood still whenever the host waited in (3), and a stream of 32 768-read batches took 1.4 ms per batch where its
     // copies take 0.45 ms.
     SKXCHK(staged_finish(st, sl));
+    if (chg.cap) {  // (the slot is idle now: its event arrays may grow)
+        SKXCHK(ensure_events(st, sl.d_ev, std::min(chg.cap, st->max_reads), chg.codes));
+        if (!sl.h_ev_n) HIPCHK(hipHostMalloc((void**)&sl.h_ev_n, 4, hipHostMallocDefault));
+        if (chg.codes && !sl.d_cons) HIPCHK(hipMalloc(&sl.d_cons, consensus_bytes(st, st->max_reads)));
+    }
     const u64 byte0 = st->packed ? base0 >> 1 : base0, rebase = st->packed ? byte0 * 2 : base0;
     const u64 n_bytes = st->packed ? ((offsets[n_reads] + 1) >> 1) - byte0 : n_bases;
     for (u32 r = 0; r <= n_reads; ++r) sl.h_offsets[r] = offsets[r] - rebase;
@@ -3472,6 +3645,7 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
     HIPCHK(hipEventRecord(sl.ev_copy, st->hs_copy));
     sl.pending = true; sl.dropped = false; sl.n_reads = n_reads; sl.n_bases = n_bases; sl.out_idx = topk_idx; sl.out_sum = reinterpret_cast<u64*>(topk_sum);
     sl.out_cons = cons;
+    sl.out_chg = chg;
     sl.ticket = st->next_ticket;
     if (ticket) *ticket = st->next_ticket;
     st->next_ticket += 1;
@@ -3517,7 +3691,7 @@ SKX_API int skx_stream_drain(skx_stream* st) {
     }
     SKXCHK(flush_pending(st));
     for (auto& sl : st->slot)
-        if (sl.in_flight) { HIPCHK(hipEventSynchronize(sl.ev_done)); sl.in_flight = false; }
+        if (sl.in_flight) { HIPCHK(hipEventSynchronize(sl.ev_done)); SKXCHK(staged_landed(st, sl)); }
     return skx_stream_sync(st);
 }
 
@@ -4306,6 +4480,53 @@ SKX_API int skx_consensus_rows(const skx_ref* ref, const uint32_t* idx, uint64_t
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpy(codes_out + r0 * n_sp * n_feat, m_out.p, (size_t)n * n_sp * n_feat * 4, hipMemcpyDeviceToHost));
     }
+    return SKX_OK;
+}
+
+// Change points of rows that live on the host: chunks of at most kChangeRowsBytes of rows through the device.  The device knows nothing of
+// the chunk before (row 0 of a chunk is an event there, as row 0 of a batch is); the host compares a chunk's first row with the last row
+// of the chunk before and drops that event when they are equal.
+static const u64 kChangeRowsBytes = 64ull << 20;
+SKX_API int skx_changes_rows(int device, const uint32_t* rows, uint64_t n_rows, uint32_t width, uint64_t cap, uint64_t* n_events,
+                             uint64_t* ev_row) {
+    if (!rows || !n_events || !ev_row) return fail(SKX_ERR_INVALID, "skx_changes_rows: NULL argument");
+    if (width < 1 || width > skx::kChangeWidthMax) return fail(SKX_ERR_INVALID, "skx_changes_rows: width = %u outside 1..%u", width, skx::kChangeWidthMax);
+    *n_events = 0;
+    if (n_rows == 0) return SKX_OK;
+    SKXCHK(use_device(device));
+    u64 chunk = std::min<u64>(n_rows, std::max<u64>(1, kChangeRowsBytes / ((u64)width * 4)));
+#ifdef SKX_EXPERIMENTS
+    if (const char* e = skx::knob("SKX_CHANGES_ROWS")) chunk = std::min<u64>(n_rows, std::max<u64>(1, strtoull(e, nullptr, 10)));  // (tests: chunks at toy size)
+#endif
+    DevMem m_rows, m_flag, m_pos, m_bsum, m_n, m_ev;
+    HIPCHK(m_rows.need((size_t)chunk * width * 4));
+    HIPCHK(m_flag.need((size_t)chunk * 4));
+    HIPCHK(m_pos.need((size_t)chunk * 4));
+    HIPCHK(m_bsum.need(((size_t)chunk / 1024 + 1) * 4));
+    HIPCHK(m_n.need(4));
+    std::vector<u32> ev;
+    u64 total = 0;
+    for (u64 r0 = 0; r0 < n_rows; r0 += chunk) {
+        const u32 n = (u32)std::min(chunk, n_rows - r0);
+        // (one entry more than the list has room for: the chunk's first event may be dropped)
+        const u32 want = (u32)std::min<u64>(n, (total < cap ? cap - total : 0) + 1);
+        HIPCHK(m_ev.need((size_t)want * 4));
+        HIPCHK(hipMemcpy(m_rows.p, rows + r0 * width, (size_t)n * width * 4, hipMemcpyHostToDevice));
+        skx::launch_change_flags(nullptr, m_rows.as<u32>(), width, 0, n, m_flag.as<u32>());
+        skx::launch_change_events(nullptr, m_flag.as<u32>(), m_pos.as<u32>(), m_bsum.as<u32>(), n, want, m_n.as<u32>(), m_ev.as<u32>(), nullptr,
+                                  nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr);
+        HIPCHK(hipGetLastError());
+        u32 n_ev = 0;
+        HIPCHK(hipMemcpy(&n_ev, m_n.p, 4, hipMemcpyDeviceToHost));
+        const u32 got = std::min(n_ev, want);
+        ev.resize(got);
+        if (got) HIPCHK(hipMemcpy(ev.data(), m_ev.p, (size_t)got * 4, hipMemcpyDeviceToHost));
+        const bool seam_equal = r0 != 0 && memcmp(rows + r0 * width, rows + (r0 - 1) * width, (size_t)width * 4) == 0;
+        const u32 first = seam_equal ? 1u : 0u;  // (event 0 of a chunk is its row 0)
+        for (u32 i = first; i < got && total + (i - first) < cap; ++i) ev_row[total + (i - first)] = r0 + ev[i];
+        total += n_ev - first;
+    }
+    *n_events = total;
     return SKX_OK;
 }
 

@@ -16,6 +16,8 @@
 //   transpose_bits_kernel  M[word][genome] -> Mq[query][genome word] (64x64 bit transposes)
 //   seg_sum / chunk_* / seg_prefix / rank_seg_top1 | rank_seg_topk | rank_seg / *_merge
 //                          running table and per-read (sum desc, index asc) top-k, pruned      (A1, A7)
+//   consensus_rows / change_flags / change_gather
+//                          behind a batch's rows: consensus codes; the reads whose call differs from the read before
 //
 // Integer work throughout (u64 hash compares, bit counts): no MFMA.
 #include <algorithm>
@@ -5207,6 +5209,71 @@ __global__ __launch_bounds__(256) void consensus_rows_kernel(const u32* __restri
     out[i] = best;
 }
 
+// ---- change points of finished rows: which rows differ from the row before them, and the short list of those that do
+// (skx_stream_bind_changes: behind a batch's ranking; skx_changes_rows: on rows the caller holds).  Integer compares only.
+// flags: rows [.][width] u32.  A row takes lpr = min(64, width rounded up to a power of two) lanes of a wave, lanes along its elements: a
+// wave compares 64 / lpr adjacent rows per step -- one contiguous stretch of memory for the row and one for its predecessor -- and four
+// steps.  Rows wider than a wave are walked 64 elements at a time and left at the first stretch that differs.  The or over a row's lanes
+// is a ballot; its first lane stores the row's flag: one u32 per row, one writer, nothing shared between launches over disjoint rows.
+__global__ __launch_bounds__(256) void change_flags_kernel(const u32* __restrict__ rows, u32 width, u32 lpr_log2, u32 ra, u32 rb,
+                                                           u32* __restrict__ flag) {
+    __builtin_amdgcn_s_setprio(3);
+    const u32 lane = lane_id(), wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const u32 lpr = 1u << lpr_log2, rpw = 64u >> lpr_log2;  // lanes per row, rows per step
+    const u32 sub = lane & (lpr - 1u), slot = lane >> lpr_log2;
+    const u64 mine = (lpr == 64u ? ~0ull : (1ull << lpr) - 1ull) << (slot * lpr);
+#pragma unroll 1
+    for (u32 step = 0; step < 4u; ++step) {
+        const u64 r64 = (u64)ra + ((u64)wave * 4u + step) * rpw + slot;
+        if ((u64)ra + ((u64)wave * 4u + step) * rpw >= rb) break;  // (wave-uniform)
+        const bool valid = r64 < rb;
+        const u32 r = (u32)r64;
+        u64 any = 0;
+        for (u32 j0 = 0; j0 < width; j0 += lpr) {
+            const u32 j = j0 + sub;
+            bool d = false;
+            if (valid && r > 0u && j < width) {
+                const size_t o = (size_t)r * width + j;
+                d = rows[o] != rows[o - width];
+            }
+            any |= __ballot(d);
+            if (lpr == 64u && any) break;  // (wave-uniform: one row per wave here)
+        }
+        if (valid && sub == 0u) flag[r] = (r == 0u || (any & mine)) ? 1u : 0u;
+    }
+}
+// events: a wave per 64 rows.  Every lane reads its row's flag and position; the flagged rows below the cap are then taken one by one
+// (wave-uniform loop over the ballot -- a handful per wave at most, usually none) and copied with the lanes along the row.  The lane on
+// the last row stores the total.
+__global__ __launch_bounds__(256) void change_gather_kernel(const u32* __restrict__ flag, const u32* __restrict__ pos, u32 n, u32 cap,
+                                                            u32* __restrict__ n_events, u32* __restrict__ ev_read,
+                                                            const u32* __restrict__ idx, const u64* __restrict__ sum, u32 w_idx,
+                                                            u32* __restrict__ ev_idx, u64* __restrict__ ev_sum,
+                                                            const u32* __restrict__ codes, u32 w_codes, u32* __restrict__ ev_codes) {
+    __builtin_amdgcn_s_setprio(3);
+    const u32 lane = lane_id();
+    const u32 r0 = (blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u;
+    if (r0 >= n) return;
+    const u32 r = r0 + lane;
+    u32 f = 0, p = 0;
+    if (r < n) { f = flag[r]; p = pos[r]; }
+    if (r == n - 1u) *n_events = p + f;
+    const bool take = f != 0u && p < cap;
+    if (take) ev_read[p] = r;
+    u64 m = __ballot(take);
+    while (m) {
+        const u32 l = (u32)__builtin_ctzll(m);
+        m &= m - 1ull;
+        const size_t src = (size_t)(r0 + l), dst = (size_t)(u32)__shfl((int)p, (int)l, 64);
+        if (ev_idx)
+            for (u32 j = lane; j < w_idx; j += 64u) ev_idx[dst * w_idx + j] = idx[src * w_idx + j];
+        if (ev_sum)
+            for (u32 j = lane; j < w_idx; j += 64u) ev_sum[dst * w_idx + j] = sum[src * w_idx + j];
+        if (ev_codes)
+            for (u32 j = lane; j < w_codes; j += 64u) ev_codes[dst * w_codes + j] = codes[src * w_codes + j];
+    }
+}
+
 // =====================================================================================
 // launchers
 // =====================================================================================
@@ -5577,6 +5644,20 @@ void launch_consensus_rows(hipStream_t st, const u32* idx, u64 first_row, u64 n_
             else SKX_CONS(64, false);
     }
 #undef SKX_CONS
+}
+void launch_change_flags(hipStream_t st, const u32* rows, u32 width, u32 ra, u32 rb, u32* flag) {
+    if (rb <= ra || width == 0 || width > kChangeWidthMax) return;
+    u32 lg = 0;
+    while (lg < 6u && (1u << lg) < width) ++lg;
+    const u32 rows_per_block = 16u * (64u >> lg);  // four waves, four steps each
+    hipLaunchKernelGGL(change_flags_kernel, dim3(cdiv(rb - ra, rows_per_block)), dim3(256), 0, st, rows, width, lg, ra, rb, flag);
+}
+void launch_change_events(hipStream_t st, const u32* flag, u32* pos, u32* bsum, u32 n, u32 cap, u32* n_events, u32* ev_read,
+                          const u32* idx, const u64* sum, u32 w_idx, u32* ev_idx, u64* ev_sum, const u32* codes, u32 w_codes, u32* ev_codes) {
+    if (n == 0) return;
+    launch_count_scan(st, flag, pos, n, bsum);
+    hipLaunchKernelGGL(change_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, flag, pos, n, cap, n_events, ev_read, idx, sum, w_idx,
+                       idx ? ev_idx : nullptr, sum ? ev_sum : nullptr, codes, w_codes, codes ? ev_codes : nullptr);
 }
 void launch_window(hipStream_t st, const u64* lo, const u64* hi, u32 n_bt, const u64* q, const u32* n_q, u32* win, u32* h_nq) {
     hipLaunchKernelGGL(window_kernel, dim3(cdiv(n_bt, 256)), dim3(256), 0, st, lo, hi, n_bt, q, n_q, win, h_nq);

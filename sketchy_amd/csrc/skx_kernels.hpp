@@ -222,6 +222,17 @@ void launch_cand_rows_back(hipStream_t st, u32* out_idx, u32 n_reads, u32 n_sp, 
 constexpr u32 kConsensusTopMax = 64;
 void launch_consensus_rows(hipStream_t st, const u32* idx, u64 first_row, u64 n_rows, u32 n_sp, u32 top_k, const u32* g0, const u32* codes,
                            u32 n_feat, u32* out, u32 n_code_rows);
+// Change points of finished rows (skx_stream_bind_changes, skx_changes_rows): rows [.][width] u32, 1 <= width <= kChangeWidthMax.
+//   flags   flag[r] = (r == 0) || rows[r] != rows[r - 1] for r in [ra, rb): one u32 per row, written by exactly one lane, so launches over
+//           disjoint [ra, rb) of one batch share nothing.  Row ra - 1 (ra > 0) must be complete in the stream's order.
+//   events  behind the flags of ALL n rows: an exclusive scan of the flags (pos, launch_count_scan's two kernels; bsum: one word per 1024
+//           rows), then every flagged row r with pos[r] < cap writes ev_read[pos] = r and copies its rows of idx (w_idx u32), sum (w_idx
+//           u64) and codes (w_codes u32) to entry pos of the optional ev_* arrays; *n_events = number of flags (not capped).  Entries from
+//           min(n_events, cap) on are not touched.  n >= 1.
+constexpr u32 kChangeWidthMax = 4096;
+void launch_change_flags(hipStream_t st, const u32* rows, u32 width, u32 ra, u32 rb, u32* flag);
+void launch_change_events(hipStream_t st, const u32* flag, u32* pos, u32* bsum, u32 n, u32 cap, u32* n_events, u32* ev_read,
+                          const u32* idx, const u64* sum, u32 w_idx, u32* ev_idx, u64* ev_sum, const u32* codes, u32 w_codes, u32* ev_codes);
 
 // dictionary
 // qrow (launch_classify) != NULL: pair_q receives ROWS of the bit matrix instead of positions in q

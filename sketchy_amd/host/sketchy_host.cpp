@@ -22,6 +22,9 @@
 //   format  M threads: the rows of a finished batch as text (src/sketchy.rs:389-400)
 //   write   in file order, by whichever format thread completes the next batch
 // Rows are the reference's, byte for byte; what changes is who does what when.
+// --changes (not in the reference): of those rows only read 1 and the reads whose lines, the shared_hashes column aside, differ from the
+// read before -- the library lists every batch's change points (skx_stream_bind_changes), format turns those into text, write drops a
+// batch's first block when the batch before ended with the same call.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -58,10 +61,15 @@ extern "C" int skx_rank_sketches(const skx_ref* ref, const uint64_t* query, cons
 extern "C" int skx_ref_set_genotypes(skx_ref* ref, uint32_t n_features, const uint32_t* codes) __attribute__((weak));
 extern "C" int skx_consensus_rows(const skx_ref* ref, const uint32_t* idx, uint64_t n_rows, uint32_t top_k, uint32_t* codes_out) __attribute__((weak));
 extern "C" int skx_stream_bind_consensus(skx_stream* st, uint32_t* codes_out) __attribute__((weak));
+// ... and the per-batch event list (`predict -s --changes`): without it the host finds the change points itself, over every read's rows.
+extern "C" int skx_stream_bind_changes(skx_stream* st, uint32_t cap, uint32_t* n_events, uint32_t* ev_read, uint32_t* ev_idx, uint64_t* ev_sum,
+                                       uint32_t* ev_codes) __attribute__((weak));
 
 namespace sketchy {
 
 struct PredictConfig { size_t top = 1, limit = 0; bool stream = false, consensus = false, header = false;
+                       // (not in the reference: print only the reads at which the call changes, see sum_of_shared_hashes)
+                       bool changes = false;
                        // (not in the reference: how the streaming pipeline is run, and whether it says how fast it was)
                        size_t threads = 0; bool timing = false, pin = false; };
 
@@ -348,6 +356,8 @@ class Sketchy {
     struct Slot {
         uint8_t* packed = nullptr; uint64_t* offsets = nullptr; uint32_t* idx = nullptr; uint64_t* sum = nullptr;
         uint32_t* cons = nullptr;  // consensus on the device: [reads][columns] codes instead of rows
+        // --changes with a library that lists a batch's change points: {n_events}, [cap] read ordinals, their rows or codes
+        uint32_t *ev_n = nullptr, *ev_read = nullptr, *ev_idx = nullptr, *ev_codes = nullptr; uint64_t* ev_sum = nullptr;
         size_t n = 0, first_read = 1;
         // what did not fit the slot (a chunk with far more / longer reads than the first records promised): heap batches the
         // device thread sends through its spill slot, one by one (rare, slow, correct)
@@ -467,9 +477,18 @@ class Sketchy {
         hip_check(skx_stream_set_packed_input(st, 1), "packed input");
 
         std::vector<Slot> slots(n_slots + 1);  // (+ the device thread's spill slot)
-        struct SlotGuard { std::vector<Slot>& s; int dev; ~SlotGuard() { for (auto& x : s) { for (void* p : {(void*)x.packed, (void*)x.offsets, (void*)x.idx, (void*)x.sum, (void*)x.cons}) if (p) skx_host_free(dev, p); } } } sguard{slots, device_};
+        struct SlotGuard { std::vector<Slot>& s; int dev; ~SlotGuard() { for (auto& x : s) { for (void* p : {(void*)x.packed, (void*)x.offsets, (void*)x.idx, (void*)x.sum, (void*)x.cons, (void*)x.ev_n, (void*)x.ev_read, (void*)x.ev_idx, (void*)x.ev_sum, (void*)x.ev_codes}) if (p) skx_host_free(dev, p); } } } sguard{slots, device_};
         const bool dev_cons = config.consensus && cons_.on;  // one code per column and read comes back, no rows
         const size_t rows_cap = dev_cons ? 0 : cap_reads * config.top;
+        // --changes: the library lists the change points of every batch (skx_stream_bind_changes; one per batch, the first read always
+        // among them) and the formatters turn only those into text.  kChangesCap entries per batch: the near-tie stream of the tests
+        // changes its top-64 row at 24 % of its reads and its top-1 row at 2 %, a sample that has found its strain a handful of times
+        // per million -- 4 096 holds a quarter of a 16 384-read batch and costs top x 12 bytes x 4 096 (3 MB at top 64) of page-locked
+        // memory per slot.  A batch with more change points than that is filtered on the host from its full rows, which therefore keep
+        // coming back; so is every batch of a library without the entry point.
+        constexpr size_t kChangesCap = 4096;
+        const size_t chg_cap = std::min(kChangesCap, cap_reads);
+        const bool dev_chg = config.changes && skx_stream_bind_changes;
         for (auto& sl : slots) {
             void* p = nullptr;
             hip_check(skx_host_alloc(device_, &p, cap_bases / 2 + 64), "batch buffer"); sl.packed = static_cast<uint8_t*>(p);
@@ -477,6 +496,15 @@ class Sketchy {
             hip_check(skx_host_alloc(device_, &p, std::max<size_t>(rows_cap, 1) * 4), "row buffer"); sl.idx = static_cast<uint32_t*>(p);
             hip_check(skx_host_alloc(device_, &p, std::max<size_t>(rows_cap, 1) * 8), "row buffer"); sl.sum = static_cast<uint64_t*>(p);
             if (dev_cons) { hip_check(skx_host_alloc(device_, &p, cap_reads * cons_.nfeat * 4), "consensus buffer"); sl.cons = static_cast<uint32_t*>(p); }
+            if (dev_chg && &sl != &slots[n_slots]) {  // (the spill slot's batches are filtered from their full rows)
+                hip_check(skx_host_alloc(device_, &p, 4), "event buffer"); sl.ev_n = static_cast<uint32_t*>(p);
+                hip_check(skx_host_alloc(device_, &p, chg_cap * 4), "event buffer"); sl.ev_read = static_cast<uint32_t*>(p);
+                if (dev_cons) { hip_check(skx_host_alloc(device_, &p, chg_cap * cons_.nfeat * 4), "event buffer"); sl.ev_codes = static_cast<uint32_t*>(p); }
+                else {
+                    hip_check(skx_host_alloc(device_, &p, chg_cap * config.top * 4), "event buffer"); sl.ev_idx = static_cast<uint32_t*>(p);
+                    hip_check(skx_host_alloc(device_, &p, chg_cap * config.top * 8), "event buffer"); sl.ev_sum = static_cast<uint64_t*>(p);
+                }
+            }
         }
         Slot& spill = slots[n_slots];
 
@@ -643,15 +671,26 @@ class Sketchy {
         }
 
         // ---- stage 3 + 4: rows as text, written in order
-        struct Job { Slot* sl = nullptr; size_t seq = 0, n = 0, first_read = 1; uint64_t ticket = 0; std::vector<uint32_t> idx, cons; std::vector<uint64_t> sum; };
+        struct Job { Slot* sl = nullptr; size_t seq = 0, n = 0, first_read = 1; uint64_t ticket = 0; std::vector<uint32_t> idx, cons; std::vector<uint64_t> sum;
+                     bool events = false; /* the slot holds the batch's event list */ };
         std::deque<Job> format_q;
         bool format_closed = false;
-        std::map<size_t, std::string> done_text;  // seq -> text, waiting for its turn
+        // seq -> text, waiting for its turn.  --changes: the text opens with the block of the batch's FIRST read (first_len bytes), which
+        // the writer drops when that read's call (first_key) is the call the batch before ended with (last_key)
+        struct Done { std::string text, first_key, last_key; size_t first_len = 0; };
+        std::map<size_t, Done> done_text;
+        std::string prev_key; bool have_prev = false;
         size_t next_write = 0;
         std::mutex write_mu;
         std::vector<std::string> mid, tail;  // per reference sketch: "\t<name>\t" and "\t<genotype columns>\n"
         if (!config.consensus)
             for (const auto& sk : sketches) { mid.push_back("\t" + sk.name + "\t"); tail.push_back("\t" + join_tab(geno.map.at(sk.name)) + "\n"); }
+        // --changes, rows: two genomes print the same lines (but for the sums) iff they share name and genotype -- line_class[g]
+        std::vector<uint32_t> line_class;
+        if (config.changes && !config.consensus) {
+            std::map<std::string, uint32_t> seen;
+            for (size_t g = 0; g < sketches.size(); ++g) line_class.push_back(seen.emplace(mid[g] + tail[g], (uint32_t)g).first->second);
+        }
         auto release_slot = [&](Slot* sl) { { std::lock_guard<std::mutex> l(mu); sl->state = 0; slot_gen[(size_t)(sl - slots.data())] += 1; } cv_free.notify_all(); };
         std::vector<std::thread> formatters;
         for (unsigned t = 0; t < n_format; ++t)
@@ -668,7 +707,52 @@ class Sketchy {
                         const uint32_t* idx = job.sl ? job.sl->idx : job.idx.data();
                         const uint64_t* sum = job.sl ? job.sl->sum : job.sum.data();
                         std::string text;
-                        if (dev_cons) {
+                        Done done;
+                        if (config.changes) {
+                            // the reads whose call may differ from the call before them: the library's events, or every read
+                            const uint32_t* codes = dev_cons ? (job.sl ? job.sl->cons : job.cons.data()) : nullptr;
+                            const bool events = job.events && *job.sl->ev_n <= chg_cap;
+                            const size_t m = events ? *job.sl->ev_n : job.n;
+                            std::string key, last, block;
+                            std::ostringstream os;
+                            for (size_t c = 0; c < m; ++c) {
+                                const size_t r = events ? job.sl->ev_read[c] : c;
+                                const uint32_t* ri = events ? (dev_cons ? nullptr : job.sl->ev_idx + c * config.top) : (dev_cons ? nullptr : idx + r * config.top);
+                                const uint64_t* rs = events ? (dev_cons ? nullptr : job.sl->ev_sum + c * config.top) : (dev_cons ? nullptr : sum + r * config.top);
+                                const uint32_t* rc = dev_cons ? (events ? job.sl->ev_codes + c * cons_.nfeat : codes + r * cons_.nfeat) : nullptr;
+                                block.clear();
+                                if (dev_cons) {
+                                    key.assign(reinterpret_cast<const char*>(rc), cons_.nfeat * 4);
+                                } else if (config.consensus) {  // (a library without the vote: the line itself, behind the read number)
+                                    os.str(std::string());
+                                    print_results(sketches, geno, ri, rs, job.first_read + r, config, os);
+                                    block = os.str();
+                                    key = block.substr(block.find('\t'));
+                                } else {
+                                    key.resize(config.top * 4);
+                                    for (size_t t2 = 0; t2 < config.top; ++t2) memcpy(&key[t2 * 4], &line_class[ri[t2]], 4);
+                                }
+                                if (c == 0) done.first_key = key;
+                                else if (key == last) continue;
+                                last = key;
+                                if (dev_cons) {
+                                    block.resize(cons_.line_cap);
+                                    block.resize((size_t)(put_consensus_line(block.data(), job.first_read + r, rc) - block.data()));
+                                } else if (!config.consensus) {
+                                    for (size_t t2 = 0; t2 < config.top; ++t2) {
+                                        const uint32_t g = ri[t2];
+                                        char num[48];
+                                        block.append(num, (size_t)(put_u64(num, job.first_read + r) - num));
+                                        block += mid[g];
+                                        block.append(num, (size_t)(put_u64(num, rs[t2]) - num));
+                                        block += tail[g];
+                                    }
+                                }
+                                text += block;
+                                if (c == 0) done.first_len = text.size();
+                            }
+                            done.last_key = last;
+                        } else if (dev_cons) {
                             const uint32_t* codes = job.sl ? job.sl->cons : job.cons.data();
                             text.resize(job.n * cons_.line_cap);
                             char* p = text.data();
@@ -695,9 +779,13 @@ class Sketchy {
                         }
                         if (job.sl) release_slot(job.sl);  // the rows are text now: the slot goes back to the parsers
                         std::lock_guard<std::mutex> w(write_mu);
-                        done_text.emplace(job.seq, std::move(text));
+                        done.text = std::move(text);
+                        done_text.emplace(job.seq, std::move(done));
                         for (auto it = done_text.find(next_write); it != done_text.end(); it = done_text.find(next_write)) {
-                            out.write(it->second.data(), (std::streamsize)it->second.size());
+                            const Done& d = it->second;
+                            const size_t skip = (config.changes && have_prev && d.first_key == prev_key) ? d.first_len : 0;
+                            out.write(d.text.data() + skip, (std::streamsize)(d.text.size() - skip));
+                            if (config.changes) { prev_key = d.last_key; have_prev = true; }
                             done_text.erase(it); ++next_write;
                         }
                     }
@@ -738,9 +826,11 @@ class Sketchy {
                     uint64_t ticket = 0;
                     const auto ts = clock::now();
                     if (dev_cons) hip_check(skx_stream_bind_consensus(st, cons), "bind consensus");
+                    const bool events = dev_chg && owner && owner->ev_n;
+                    if (events) hip_check(skx_stream_bind_changes(st, (uint32_t)chg_cap, owner->ev_n, owner->ev_read, owner->ev_idx, owner->ev_sum, owner->ev_codes), "bind changes");
                     hip_check(skx_stream_submit(st, packed, offsets, (uint32_t)n, dev_cons ? nullptr : idx, dev_cons ? nullptr : sum, &ticket), "submit");
                     s_submit += since(ts);
-                    Job j; j.sl = owner; j.seq = seq_no++; j.n = n; j.first_read = fed + 1; j.ticket = ticket;
+                    Job j; j.sl = owner; j.seq = seq_no++; j.n = n; j.first_read = fed + 1; j.ticket = ticket; j.events = events;
                     fed += n; ++n_batches;
                     in_flight.emplace_back(owner, std::move(j));
                     const auto tr = clock::now();
@@ -884,8 +974,9 @@ static void usage() {
     std::fprintf(stderr,
                  "sketchy-hip sketch  -o OUT.msh [-i GENOME.fa[.gz] ...] [-s SIZE=1000] [-k K=16] [-e SEED=0] [--counts]   (paths on stdin without -i;\n"
                  "                    --counts: also write every hash's abundance, Mash's counts32)\n"
-                 "sketchy-hip predict -r REF.msh -g GENO.tsv [-i READS.fx[.gz] ...] [-t TOP] [-l LIMIT] [-s] [-c] [-H] [-b BATCH_READS] [-j THREADS] [--timing] [--pin]\n"
-                 "                    (without -s: several inputs, one sample each -- the rows of every sample in input order; -l per input; -s: one input)\n"
+                 "sketchy-hip predict -r REF.msh -g GENO.tsv [-i READS.fx[.gz] ...] [-t TOP] [-l LIMIT] [-s] [-c] [-H] [-x] [-b BATCH_READS] [-j THREADS] [--timing] [--pin]\n"
+                 "                    (without -s: several inputs, one sample each -- the rows of every sample in input order; -l per input; -s: one input;\n"
+                 "                    -x / --changes, with -s: only read 1 and the reads whose lines, the shared_hashes column aside, differ from the read before)\n"
                  "sketchy-hip shared  -r REF.msh -q QUERY.msh\n"
                  "sketchy-hip info    -i SKETCH.msh [-p]\n"
                  "sketchy-hip check   -r REF.msh -g GENO.tsv\n");
@@ -899,7 +990,7 @@ int main(int argc, char** argv) {
     const std::map<std::string, std::string> longnames = {{"--input", "-i"}, {"--reference", "-r"}, {"--genotypes", "-g"}, {"--top", "-t"}, {"--limit", "-l"},
                                                           {"--stream", "-s"}, {"--consensus", "-c"}, {"--header", "-H"}, {"--query", "-q"}, {"--params", "-p"},
                                                           {"--device", "-d"}, {"--batch", "-b"}, {"--output", "-o"}, {"--sketch-size", "-s"},
-                                                          {"--kmer-size", "-k"}, {"--seed", "-e"}, {"--threads", "-j"}, {"--timing", "-T"}, {"--pin", "-P"}, {"--counts", "-C"}};
+                                                          {"--kmer-size", "-k"}, {"--seed", "-e"}, {"--threads", "-j"}, {"--timing", "-T"}, {"--pin", "-P"}, {"--counts", "-C"}, {"--changes", "-x"}};
     const bool is_sketch = cmd == "sketch";  // there -s takes a value (sketch size), elsewhere it is --stream
     const bool many_inputs = is_sketch || cmd == "predict";
     for (int i = 2; i < argc; ++i) {
@@ -908,7 +999,7 @@ int main(int argc, char** argv) {
         if (longnames.count(a)) a = longnames.at(a);
         // (predict: a lone "-" is a path -- stdin)
         if (many_inputs && a == "-i") { while (i + 1 < argc && (argv[i + 1][0] != '-' || (!is_sketch && !argv[i + 1][1]))) inputs.push_back(argv[++i]); continue; }
-        if ((!is_sketch && a == "-s") || a == "-c" || a == "-H" || a == "-p" || a == "-T" || a == "-P" || a == "-C") flag[a] = true;
+        if ((!is_sketch && a == "-s") || a == "-c" || a == "-H" || a == "-p" || a == "-T" || a == "-P" || a == "-C" || a == "-x") flag[a] = true;
         else if (i + 1 < argc) opt[a] = argv[++i];
         else { usage(); return 2; }
     }
@@ -928,6 +1019,10 @@ int main(int argc, char** argv) {
                        flag["-C"]);
         } else if (cmd == "predict") {
             if (!opt.count("-r") || !opt.count("-g")) { usage(); return 2; }
+            if (flag["-x"] && !flag["-s"]) {
+                std::fprintf(stderr, "Error: predict --changes prints the change points of a stream: it needs -s\n");
+                return 2;
+            }
             if (flag["-s"] && inputs.size() > 1) {
                 std::fprintf(stderr, "Error: predict -s (streaming) takes one input, %zu were given: several inputs are ranked offline (without -s)\n", inputs.size());
                 return 2;
@@ -935,7 +1030,7 @@ int main(int argc, char** argv) {
             sketchy::PredictConfig cfg;
             cfg.top = opt.count("-t") ? (size_t)std::atol(opt["-t"].c_str()) : 1;
             cfg.limit = opt.count("-l") ? (size_t)std::atol(opt["-l"].c_str()) : 0;
-            cfg.stream = flag["-s"]; cfg.consensus = flag["-c"]; cfg.header = flag["-H"];
+            cfg.stream = flag["-s"]; cfg.consensus = flag["-c"]; cfg.header = flag["-H"]; cfg.changes = flag["-x"];
             cfg.threads = opt.count("-j") ? (size_t)std::max(1L, std::atol(opt["-j"].c_str())) : 0; cfg.timing = flag["-T"]; cfg.pin = flag["-P"];
             app.predict(inputs, opt["-r"], opt["-g"], cfg, std::cout);
         } else if (cmd == "shared") {

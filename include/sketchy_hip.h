@@ -409,6 +409,9 @@ int skx_sketch_groups_counts(int device, uint32_t k, uint64_t seed, uint32_t s, 
 /*
  * common[q][g] = |query sketch q  intersect  reference genome g|  (src/sketchy.rs:419-438) for
  * n_query ascending sketches laid out like skx_ref_create's input (row stride q_stride).
+ * Any 64-bit value is an ordinary hash, in the reference and in a query: 0xFFFFFFFFFFFFFFFE and 0xFFFFFFFFFFFFFFFF (which the
+ * library keeps outside its matrix, as exceptions) count for exactly the genomes that hold that very value -- a query's ...FE shares
+ * nothing with a reference that holds only ...FF, and the other way round.
  */
 int skx_common_hashes(const skx_ref *ref, const uint64_t *query, const uint32_t *query_len, uint32_t n_query,
                       uint32_t q_stride, uint32_t *common);

@@ -2029,8 +2029,10 @@ static int queue_static_scan(skx_stream* st, int b) {
     static const bool big_slices = skx::knob("SKX_SCAN_BIGSLICE") && atoi(skx::knob("SKX_SCAN_BIGSLICE")) != 0;
     {
         Span sp(st, 2, st->hs);
+        // (the stream's slabs only under the experiments build's SKX_SCAN_ABLATE: with them launch_scan picks the ablated kernel, which
+        // writes no results -- a negative control must see the static rows go wrong, tests/test_gpu_hash_classes.py)
         skx::launch_scan(st->hs, ref->d_mat, ref->s, ref->n_tiles, ref->rb, ref->n_bands, ref->d_qs, ref->d_win_s, st->d_ms[b], nullptr, ref->n_pad,
-                         false, true, nullptr, st->d_mdirty_s, true, 0u, big_slices);
+                         false, true, skx::scan_ablated() ? st->d_hbuf : nullptr, st->d_mdirty_s, true, 0u, big_slices);
     }
     {
         Span sp(st, 1, st->hs);

@@ -1825,7 +1825,15 @@ __global__ __launch_bounds__(256) void classify_a_kernel(const u64* __restrict__
         c[j] = 0; info[j] = kSlotNone;
         if (q0 + j < nq) {
             const u64 h = q[q0 + j];
-            if (h >= kEmpty) c[j] = 1u;  // (lifted hashes: exceptions_kernel sets their bits; they ride with the dense rows)
+            if (h >= kEmpty) {  // (lifted hashes: exceptions_kernel sets their bits; they ride with the dense rows)
+                // static dictionary: only a lifted hash that some genome holds has a row in the tail; one that none holds goes with the
+                // "no genome holds it" rows behind (kSlotNone: an empty list) -- classify_c's search in the tail finds every dense one exactly
+                c[j] = 1u;
+                if (ri.qs) {
+                    const u32 nt = ri.n_sd > ri.tail0 ? ri.n_sd - ri.tail0 : 0u, at = lower_bound_u64(ri.qs + ri.tail0, nt, h);
+                    c[j] = at < nt && ri.qs[ri.tail0 + at] == h ? 1u : 0u;
+                }
+            }
             else {
                 u32 slot = kt_start(h, ri.mask);
                 for (;;) {
@@ -5694,6 +5702,14 @@ bool scan_lean_wants_slabs() {
 #endif
 }
 bool scan_lean_into_m() { return !scan_lean_wants_slabs(); }
+bool scan_ablated() {
+#ifdef SKX_EXPERIMENTS
+    static const int ablate = env_int("SKX_SCAN_ABLATE", 0);
+    return ablate != 0;
+#else
+    return false;
+#endif
+}
 void launch_word_bands(hipStream_t st, u32* win, u32 n_tiles, u32 n_bands, const u32* n_q, u32* wb, const u64* lo, const u64* hi,
                        const u64* q, u32* h_nq) {
     hipLaunchKernelGGL(word_bands_kernel, dim3(n_tiles), dim3(256), 0, st, win, n_tiles, n_bands, n_q, wb, lo, hi, q, h_nq);

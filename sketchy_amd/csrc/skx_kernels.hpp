@@ -272,6 +272,9 @@ bool scan_lean_applies(u32 n_bands, bool split, bool big_table);
 u32 scan_lean_words();
 bool scan_lean_wants_slabs();
 bool scan_lean_into_m();
+// (experiments build: the profiling aid SKX_SCAN_ABLATE is set -- the scan of the static dense dictionary then takes the ablated kernels
+// too, like a per-pass dictionary's; the product library: false)
+bool scan_ablated();
 // run > 0: scan_run_kernel -- one workgroup per `run` consecutive bands of a tile, results OR-ed into m_bits (no slabs, no hbuf);
 // windows of up to scan_run_cap() entries in one pass over the rows
 u32 scan_run_cap();

@@ -21,6 +21,7 @@
  *                             collections (the `shared` all-pairs use at :251-261)
  *   skx_rank_sketches      <- the tail of Sketchy::_shared_hashes (src/sketchy.rs:304-312): shared hashes against every
  *                             genome, stable sort, first `top` rows -- for many pooled sketches in one call
+ *   skx_ref_neighbours     <- no counterpart: the same tail for every genome of the resident reference against the others of its species
  *   skx_predict_groups     <- all of Sketchy::_shared_hashes (src/sketchy.rs:281-315) for many samples: pool, count, rank
  *   skx_stream_bind_changes / skx_changes_rows <- no counterpart: the reference prints every read's rows (:348-349, :391-399); these
  *                             report only the reads at which what it would print (indices or consensus) differs from the read before
@@ -439,6 +440,22 @@ int skx_predict_groups(const skx_ref *ref, const uint8_t *bases, const uint64_t 
  * Errors (all found before any device work): NULL argument, top_k outside 1..SKX_MAX_TOP, no genotype table on the reference, an
  * index >= its species' genome count: SKX_ERR_INVALID.  n_rows == 0: SKX_OK, nothing is touched. */
 int skx_consensus_rows(const skx_ref *ref, const uint32_t *idx, uint64_t n_rows, uint32_t top_k, uint32_t *codes_out);
+/* Leave-one-out neighbours of the resident reference (no counterpart in the reference binary; the question its "Sketch validation"
+ * section asks): for every genome g of [first, first + count) of `species` (indices local to the species) the first top_k genomes OF
+ * THE SAME SPECIES OTHER THAN g in (shared hashes desc, index asc) order, shared = |column g  intersect  column h| by plain set
+ * intersection (src/sketchy.rs:425-438; hashes >= 0xFFFFFFFFFFFFFFFE count like any other) -- what offline `predict` of g's own sketch
+ * would print against a reference that lacks g.  g is left out INSIDE the selection: it ties with every duplicate of itself and with
+ * every genome that contains its sketch, and among ties the lower index wins, so g need not be among the first top_k + 1 rows of a
+ * plain ranking (a caller taking it out afterwards has to look for it), and at top_k = SKX_MAX_TOP there is no top_k + 1 to ask for.
+ * nb_idx / nb_shared: host arrays [count][top_k].  codes_out: optional [count][n_features], the consensus of each row's neighbours
+ * (skx_ref_set_genotypes: semantics, tie rule), voted on the device; non-NULL without a genotype table is SKX_ERR_INVALID.
+ * top_k: 1 .. min(genomes of the species - 1, SKX_MAX_TOP).
+ * The query rows never exist on the host: a kernel rebuilds them from the resident matrix and the exception list, in chunks of at most
+ * 256 MiB of rows; the counting and the selection are skx_rank_sketches' (every species is counted, the species' own segment is ranked).
+ * Errors (all found before any device work): NULL required pointer, species out of range, first + count beyond the species, top_k out of
+ * range: SKX_ERR_INVALID.  count == 0: SKX_OK, nothing is touched. */
+int skx_ref_neighbours(const skx_ref *ref, uint32_t species, uint32_t first, uint32_t count, uint32_t top_k,
+                       uint32_t *nb_idx, uint32_t *nb_shared, uint32_t *codes_out);
 
 /* The same operator alone on rows the caller holds (host): the change points of n_rows rows of `width` u32 each, row 0 included.
  * ev_row [cap] receives the first min(n_events, cap) of them (row indices, ascending; nothing past them is touched), *n_events their

@@ -76,6 +76,7 @@ SYMBOLS = [
     ("skx_common_hashes", _i, [_vp, _vp, _vp, _u32, _u32, _vp]),
     ("skx_rank_sketches", _i, [_vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("skx_consensus_rows", _i, [_vp, _vp, _u64, _u32, _vp]),
+    ("skx_ref_neighbours", _i, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("skx_changes_rows", _i, [_i, _vp, _u64, _u32, _u64, C.POINTER(_u64), _vp]),
     ("skx_predict_groups", _i, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("skx_comm_unique_id", _i, [_vp]),

@@ -246,6 +246,31 @@ class ReferenceSketch:
         _lib.check(_lib.load().skx_consensus_rows(self._h, _p(idx), n_rows, top, _p(out)))
         return out
 
+    def neighbours(self, first=0, count=None, top=1, species=0, want_codes=False):
+        """Leave-one-out neighbours: for every genome of [first, first + count) of `species` (count None: to the species' end) the
+        first `top` OTHER genomes of that species in (shared hashes desc, index asc) order, rebuilt, counted and selected on the
+        device from the resident reference.  Returns (idx, shared[, codes]): [count, top] uint32 each (indices local to the species)
+        [, [count, n_features] uint32: the consensus of each row's neighbours, ties to the smallest code]."""
+        species, first, top = int(species), int(first), int(top)
+        if not 0 <= species < self.n_species:
+            raise ValueError(f"species {species} outside 0..{self.n_species - 1}")
+        n = self.species[species]
+        count = n - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > n:
+            raise ValueError(f"first={first} + count={count} exceeds the species' {n} genomes")
+        if not 1 <= top <= min(n - 1, _lib.MAX_TOP):
+            raise ValueError(f"top={top} outside 1..min(genomes of the species - 1, {_lib.MAX_TOP}) = {min(n - 1, _lib.MAX_TOP)}")
+        idx = np.zeros((count, top), np.uint32)
+        shared = np.zeros_like(idx)
+        codes = None
+        if want_codes:
+            nf = self.n_features
+            if nf == 0:
+                raise ValueError("want_codes needs a genotype table (set_genotypes)")
+            codes = np.zeros((count, nf), np.uint32)
+        _lib.check(_lib.load().skx_ref_neighbours(self._h, species, first, count, top, _p(idx), _p(shared), _p(codes) if want_codes else None))
+        return (idx, shared, codes) if want_codes else (idx, shared)
+
     def close(self):
         if getattr(self, "_h", None):
             _lib.load().skx_ref_destroy(self._h)

@@ -4452,6 +4452,80 @@ SKX_API int skx_predict_groups(const skx_ref* ref, const uint8_t* bases, const u
     return SKX_OK;
 }
 
+// Leave-one-out neighbours of the resident reference.  The queries are the reference's own columns: ref_rows_kernel turns a chunk of them
+// back into the full-width rows rank_sketches_checked uploads (at most kNeighbourRowsBytes of them at a time), the counting is the same
+// passes into padded counts, and the selection leaves every row's own genome out (row_topk_kernel<true>): it ties with every genome that
+// holds its whole sketch, so it need not be among the first top_k + 1 of a plain ranking, and SKX_MAX_TOP + 1 rows cannot be asked for.
+static const u64 kNeighbourRowsBytes = 256ull << 20;
+SKX_API int skx_ref_neighbours(const skx_ref* ref, uint32_t species, uint32_t first, uint32_t count, uint32_t top_k, uint32_t* nb_idx,
+                               uint32_t* nb_shared, uint32_t* codes_out) {
+    SKXCHK(check_top_range("skx_ref_neighbours", top_k));
+    if (!ref || !nb_idx || !nb_shared) return fail(SKX_ERR_INVALID, "skx_ref_neighbours: NULL argument");
+    if (species >= ref->n_species) return fail(SKX_ERR_INVALID, "skx_ref_neighbours: species=%u outside 0..%u", species, ref->n_species - 1);
+    const u32 n = ref->sp_n[species];
+    if (first > n || count > n - first)
+        return fail(SKX_ERR_INVALID, "skx_ref_neighbours: first=%u + count=%u exceeds the species' n_genomes=%u", first, count, n);
+    if (top_k > n - 1) return fail(SKX_ERR_INVALID, "skx_ref_neighbours: top_k=%u exceeds the species' other genomes (n_genomes - 1 = %u)", top_k, n - 1);
+    if (codes_out && !ref->d_codes) return fail(SKX_ERR_INVALID, "skx_ref_neighbours: codes_out given, but the reference has no genotype table");
+    if (count == 0) return SKX_OK;
+    const u32 s = ref->s, n_pad = ref->n_pad, n_feat = ref->n_features;
+    u32 chunk = (u32)std::min<u64>(count, std::max<u64>(1, kNeighbourRowsBytes / ((u64)s * 8)));
+#ifdef SKX_EXPERIMENTS
+    if (const char* e = skx::knob("SKX_NEIGHBOUR_CHUNK")) chunk = (u32)std::min<u64>(count, std::max<u64>(1, strtoull(e, nullptr, 10)));  // (tests: chunks at toy size)
+#endif
+    skx_stream* st = nullptr;
+    SKXCHK(stream_create_internal(&st, ref, 0, chunk, 1, s, s, true));  // (whole sketches: every hash is a pair)
+    DevMem m_len, m_cnt, m_idx, m_val, m_codes;
+    std::vector<u32> len(chunk);
+    int rc = SKX_OK;
+    for (u32 c0 = 0; c0 < count && rc == SKX_OK; c0 += chunk) {
+        const u32 nq = std::min(chunk, count - c0), g_first = first + c0;  // this chunk: genomes [g_first, g_first + nq) of the species
+        // ---- the query rows, from the matrix (every stream of the handle is idle: each pass below ends with a synchronisation)
+        hipError_t e = use_rows(st);
+        if (e == hipSuccess) e = m_len.need((size_t)chunk * 4);
+        if (e == hipSuccess) {
+            skx::launch_ref_rows(nullptr, ref->d_mat, s, ref->sp_g0[species] + g_first, nq, ref->d_exc_g, ref->d_exc_h, ref->n_exc, st->d_sk, s, m_len.as<u32>());
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(len.data(), m_len.p, (size_t)nq * 4, hipMemcpyDeviceToHost);  // (behind the two kernels)
+        if (e != hipSuccess) { rc = fail(SKX_ERR_HIP, "skx_ref_neighbours rows: %s", hipGetErrorString(e)); break; }
+        // candidate prefix of every query: all of it -- a row holds reference hashes only, none above max_ref
+        st->h_poff[0] = 0;
+        for (u32 i = 0; i < nq; ++i) st->h_poff[i + 1] = st->h_poff[i] + len[i];
+        e = hipMemcpy(st->d_poff, st->h_poff, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { rc = fail(SKX_ERR_HIP, "skx_ref_neighbours upload: %s", hipGetErrorString(e)); break; }
+        const u32 out_cap = (u32)std::max<u64>(1, (256ull << 20) / ((u64)n_pad * 4));
+        rc = for_each_pass(st, nq, out_cap, [&](u32 ra, u32 rb, u32 p_base, u32 P) -> int {
+            const u32 rows = rb - ra;
+            HIPCHK(m_cnt.need((size_t)rows * n_pad * 4));
+            HIPCHK(m_idx.need((size_t)rows * top_k * 4));
+            HIPCHK(m_val.need((size_t)rows * top_k * 4));
+            if (codes_out) HIPCHK(m_codes.need((size_t)rows * n_feat * 4));
+            u32 bound = 0;  // no count of the pass exceeds its longest query
+            for (u32 i = ra; i < rb; ++i) bound = std::max(bound, len[i]);
+            if (P == 0) {  // empty columns only: all-zero counts
+                HIPCHK(hipMemsetAsync(m_cnt.p, 0, (size_t)rows * n_pad * 4, st->hs2));
+            } else {
+                SKXCHK(run_pass(st, ra, rb, p_base, P, nullptr, nullptr, nullptr, false, false, 0xFFFFFFFFu, nullptr, m_cnt.as<u32>()));
+                SKXCHK(queue_chains(st, true));
+            }
+            skx::launch_row_topk_excl(st->hs2, m_cnt.as<u32>(), rows, n_pad, ref->species(), species, g_first + ra, top_k, bound, m_idx.as<u32>(), m_val.as<u32>());
+            if (codes_out)
+                skx::launch_consensus_rows(st->hs2, m_idx.as<u32>(), 0, rows, 1, top_k, ref->d_sp_g0 + species, ref->d_codes, n_feat, m_codes.as<u32>(), n_pad);
+            HIPCHK(hipGetLastError());
+            const size_t out_at = (size_t)(c0 + ra) * top_k, out_n = (size_t)rows * top_k * 4;
+            HIPCHK(hipMemcpyAsync(nb_idx + out_at, m_idx.p, out_n, hipMemcpyDeviceToHost, st->hs2));
+            HIPCHK(hipMemcpyAsync(nb_shared + out_at, m_val.p, out_n, hipMemcpyDeviceToHost, st->hs2));
+            if (codes_out)
+                HIPCHK(hipMemcpyAsync(codes_out + (size_t)(c0 + ra) * n_feat, m_codes.p, (size_t)rows * n_feat * 4, hipMemcpyDeviceToHost, st->hs2));
+            HIPCHK(hipStreamSynchronize(st->hs2));
+            return SKX_OK;
+        });
+    }
+    stream_free(st);
+    return rc;
+}
+
 // Consensus codes of ranked rows that live on the host: checks first, then chunks of rows through the device (kConsRowsBytes of index rows
 // or of codes at a time, whichever is larger per row)
 static const u64 kConsRowsBytes = 64ull << 20;
@@ -4680,6 +4754,23 @@ SKX_API int skx_debug_row_topk(int device, const uint32_t* counts, uint32_t n_ro
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(top_idx, m_idx.p, (size_t)n_rows * top_k * 4, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(top_val, m_val.p, (size_t)n_rows * top_k * 4, hipMemcpyDeviceToHost));
+    return SKX_OK;
+}
+// experiments build only: the query rows skx_ref_neighbours rebuilds for genomes [first, first + count) of a species, as they lie on the
+// device -- rows [count][stride] (the reference's column stride), len [count]
+SKX_API int skx_debug_ref_rows(const skx_ref* ref, uint32_t species, uint32_t first, uint32_t count, uint64_t* rows, uint32_t* len) {
+    if (!ref || !rows || !len || species >= ref->n_species) return fail(SKX_ERR_INVALID, "skx_debug_ref_rows: bad argument");
+    if (count < 1 || first > ref->sp_n[species] || count > ref->sp_n[species] - first) return fail(SKX_ERR_INVALID, "skx_debug_ref_rows: bad range");
+    SKXCHK(use_device(ref->device));
+    DevMem m_rows, m_len;
+    HIPCHK(m_rows.need((size_t)count * ref->s * 8));
+    HIPCHK(m_len.need((size_t)count * 4));
+    HIPCHK(hipMemset(m_rows.p, 0xA5, (size_t)count * ref->s * 8));  // (every slot has to be written)
+    skx::launch_ref_rows(nullptr, ref->d_mat, ref->s, ref->sp_g0[species] + first, count, ref->d_exc_g, ref->d_exc_h, ref->n_exc, m_rows.as<u64>(), ref->s,
+                         m_len.as<u32>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpy(rows, m_rows.p, (size_t)count * ref->s * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(len, m_len.p, (size_t)count * 4, hipMemcpyDeviceToHost));
     return SKX_OK;
 }
 #endif

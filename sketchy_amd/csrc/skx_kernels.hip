@@ -91,6 +91,78 @@ __global__ __launch_bounds__(256) void ref_tile_kernel(const u64* __restrict__ s
     }
 }
 
+// =====================================================================================
+// the way back: genomes [p0, p0 + cnt) of the resident matrix as full-width query rows (skx_ref_neighbours)
+// =====================================================================================
+// rows[p - p0][r] = mat[p / 256][r][p % 256], entries >= kEmpty (padding; lifted hashes are not in the matrix) written as 0.
+// A genome's consecutive ranks lie 2 KB apart while the 64 genomes of one aligned group hold one rank in 512 contiguous bytes, so a
+// workgroup turns a block of 64 ranks x 64 genomes in LDS: it reads with lanes along the genome axis (one wave = one rank = 512 B)
+// and writes with lanes along the rank axis (one wave = one genome's 64 ranks = 512 B of its row).
+// grid: (ceil(s / 64), aligned groups of 64 padded genomes that meet the chunk); lanes outside [p0, p0 + cnt) or past rank s - 1
+// neither load nor store, so a chunk may begin and end anywhere: inside a tile, across the tile boundary, at a species' padded start.
+// LDS pitch 65 u64 per rank (33 280 B).  Phase 1 stores tile[rank][lane]: a 64-bit LDS store is served in four groups of 16
+// neighbouring lanes on 32 banks of 4 B; 16 consecutive u64 cover the 32 banks once each -- no conflict at any pitch.  Phase 2 loads
+// tile[lane][genome]: a 64-bit LDS load is served in two groups of 32 lanes on 64 banks; lane l starts at dword 2 * (65 l + genome), bank
+// (2 l + 2 genome) mod 64 -- 32 distinct even banks, each with its odd neighbour: no conflict.  At pitch 64 all 32 lanes of a group
+// would start on the same bank (32-way); any odd pitch does, 65 is the smallest.
+constexpr u32 kRowsTile = 64, kRowsPitch = 65;
+__global__ __launch_bounds__(256) void ref_rows_kernel(const u64* __restrict__ mat, u32 s, u32 p0, u32 cnt, u64* __restrict__ rows, u32 row_stride) {
+    __shared__ u64 tile[kRowsTile * kRowsPitch];
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u32 r0 = blockIdx.x * kRowsTile;
+    const u32 pg = (p0 / kRowsTile + blockIdx.y) * kRowsTile;  // first padded genome of this group (64 | 256: inside one tile)
+    {
+        const u32 p = pg + lane;
+        const bool mine = p >= p0 && p - p0 < cnt;
+        const u64* col = mat + (size_t)(p / kTileGenomes) * s * kTileGenomes + p % kTileGenomes;
+        u64 v[kRowsTile / 4];
+#pragma unroll
+        for (u32 j = 0; j < kRowsTile / 4u; ++j) {
+            const u32 r = r0 + 4u * j + wv;
+            v[j] = (mine && r < s) ? col[(size_t)r * kTileGenomes] : kPad;
+        }
+#pragma unroll
+        for (u32 j = 0; j < kRowsTile / 4u; ++j) tile[(4u * j + wv) * kRowsPitch + lane] = v[j];
+    }
+    __syncthreads();
+    const u32 r = r0 + lane;
+#pragma unroll
+    for (u32 j = 0; j < kRowsTile / 4u; ++j) {
+        const u32 gi = 4u * j + wv, p = pg + gi;  // (wave-uniform)
+        if (p >= p0 && p - p0 < cnt && r < s) {
+            const u64 x = tile[lane * kRowsPitch + gi];
+            rows[(size_t)(p - p0) * row_stride + r] = x >= kEmpty ? 0ull : x;
+        }
+    }
+}
+// ... and what the matrix does not say by itself.  One thread per genome of the chunk: the length of its column in the matrix (entries
+// below kEmpty are a prefix: bisection), then its lifted hashes -- exc_g ascending by padded genome, a genome's hashes one after the
+// other in DESCENDING order, as skx_ref_create lists them -- appended in ascending order behind that prefix; len[i] = both together.
+// Runs behind ref_rows_kernel (which has zeroed the slots it fills).
+__global__ __launch_bounds__(256) void ref_rows_tail_kernel(const u64* __restrict__ mat, u32 s, u32 p0, u32 cnt, const u32* __restrict__ exc_g,
+                                                            const u64* __restrict__ exc_h, u32 n_exc, u64* __restrict__ rows, u32 row_stride,
+                                                            u32* __restrict__ len) {
+    const u32 i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= cnt) return;
+    const u32 p = p0 + i;
+    const u64* col = mat + (size_t)(p / kTileGenomes) * s * kTileGenomes + p % kTileGenomes;
+    u32 lo = 0, hi = s;  // first rank whose entry is >= kEmpty
+    while (lo < hi) {
+        const u32 mid = (lo + hi) >> 1;
+        if (col[(size_t)mid * kTileGenomes] < kEmpty) lo = mid + 1; else hi = mid;
+    }
+    u32 n = lo;
+    u32 a = 0, b = n_exc;  // first exception of a genome >= p
+    while (a < b) {
+        const u32 mid = (a + b) >> 1;
+        if (exc_g[mid] < p) a = mid + 1; else b = mid;
+    }
+    u32 z = a;
+    while (z < n_exc && exc_g[z] == p) ++z;
+    for (u32 e = z; e > a && n < row_stride; --e) rows[(size_t)i * row_stride + n++] = exc_h[e - 1];
+    len[i] = n;
+}
+
 // per (band b, tile t): smallest and largest real hash in the band's rows.  One block per (b,t).
 __global__ __launch_bounds__(256) void band_bounds_kernel(const u64* __restrict__ mat, u32 s, u32 n_tiles, u32 rb,
                                                           u64* __restrict__ lo, u64* __restrict__ hi) {
@@ -4176,18 +4248,23 @@ __global__ __launch_bounds__(256) void shared_debug_kernel(const u32* __restrict
 //      of the counts == T the first top_k - (number above) in ascending index;
 //   3. the top_k kept entries are ordered by counting ranks in one wave.
 // Integer and deterministic; the only atomics are the histogram's, in LDS.
+// EXCL (skx_ref_neighbours): a row is ranked in ONE species (`only_sp`; one workgroup per row) with one genome of it, excl0 + row, absent
+// from the histogram and from the sweep -- the first top_k of the others; top_k <= n - 1.  Without EXCL the two arguments are unused
+// and the code is what it was.
+template <bool EXCL>
 __global__ __launch_bounds__(256) void row_topk_kernel(const u32* __restrict__ cnt, u32 n_pad, Species sp, u32 top_k, u32 bound,
-                                                       u32* __restrict__ top_idx, u32* __restrict__ top_val) {
+                                                       u32* __restrict__ top_idx, u32* __restrict__ top_val, u32 only_sp, u32 excl0) {
     __shared__ u32 hist[256];
     __shared__ u32 s_sel[2];      // the bytes chosen so far; entries still wanted among the counts that share them
     __shared__ u32 wcnt[2][8];    // per tile parity: the four waves' entries above T, then equal to T
     __shared__ u32 kept_v[kRowTopkMax], kept_i[kRowTopkMax];
     static_assert(kRowTopkMax == 64, "one wave orders the kept entries");
-    const u32 row = blockIdx.x / sp.n_sp, s_ = blockIdx.x % sp.n_sp;
+    const u32 row = EXCL ? blockIdx.x : blockIdx.x / sp.n_sp, s_ = EXCL ? only_sp : blockIdx.x % sp.n_sp;
     const u32 n = sp.n[s_];
+    const u32 ex = EXCL ? excl0 + row : 0xFFFFFFFFu;  // (no genome has that index)
     const u32* __restrict__ v = cnt + (size_t)row * n_pad + sp.g0[s_];
     const u32 tid = threadIdx.x, lane = lane_id(), wv = tid >> 6;
-    if (top_k == 0 || top_k > kRowTopkMax || top_k > n) return;  // (the entry point has checked; uniform)
+    if (top_k == 0 || top_k > kRowTopkMax || top_k > n - (EXCL ? 1u : 0u)) return;  // (the entry point has checked; uniform)
     // ---- 1. the top_k-th largest count
     u32 prefix = 0, want = top_k;
     if (tid == 0) { s_sel[0] = 0; s_sel[1] = top_k; }
@@ -4198,6 +4275,7 @@ __global__ __launch_bounds__(256) void row_topk_kernel(const u32* __restrict__ c
         __syncthreads();
         for (u32 g = tid; g < n; g += 256u) {
             const u32 x = v[g];
+            if (EXCL && g == ex) continue;
             if ((x & himask) == prefix) atomicAdd(&hist[(x >> shift) & 255u], 1u);
         }
         __syncthreads();
@@ -4229,7 +4307,8 @@ __global__ __launch_bounds__(256) void row_topk_kernel(const u32* __restrict__ c
     for (u32 t0 = 0; t0 < n; t0 += 256u) {
         const u32 g = t0 + tid, par = (t0 >> 8) & 1u;
         const u32 x = g < n ? v[g] : 0u;
-        const bool ab = g < n && x > T, eq = g < n && x == T;
+        const bool in = g < n && !(EXCL && g == ex);
+        const bool ab = in && x > T, eq = in && x == T;
         const u64 ma = __ballot(ab), me = __ballot(eq);
         if (lane == 0) { wcnt[par][wv] = (u32)__popcll(ma); wcnt[par][4u + wv] = (u32)__popcll(me); }
         __syncthreads();  // (one barrier per tile: the counters alternate between two sets)
@@ -5917,7 +5996,19 @@ void launch_shared_debug(hipStream_t st, const u32* pair_q, const u32* poff, u32
 }
 void launch_row_topk(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, const Species& sp, u32 top_k, u32 bound, u32* top_idx, u32* top_val) {
     if (n_rows == 0) return;
-    hipLaunchKernelGGL(row_topk_kernel, dim3(n_rows * sp.n_sp), dim3(256), 0, st, cnt, n_pad, sp, top_k, bound, top_idx, top_val);
+    hipLaunchKernelGGL(row_topk_kernel<false>, dim3(n_rows * sp.n_sp), dim3(256), 0, st, cnt, n_pad, sp, top_k, bound, top_idx, top_val, 0u, 0u);
+}
+void launch_row_topk_excl(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, const Species& sp, u32 species, u32 excl0, u32 top_k, u32 bound,
+                          u32* top_idx, u32* top_val) {
+    if (n_rows == 0) return;
+    hipLaunchKernelGGL(row_topk_kernel<true>, dim3(n_rows), dim3(256), 0, st, cnt, n_pad, sp, top_k, bound, top_idx, top_val, species, excl0);
+}
+void launch_ref_rows(hipStream_t st, const u64* mat, u32 s, u32 p0, u32 cnt, const u32* exc_g, const u64* exc_h, u32 n_exc, u64* rows,
+                     u32 row_stride, u32* len) {
+    if (cnt == 0) return;
+    const u32 groups = (p0 + cnt - 1) / kRowsTile - p0 / kRowsTile + 1;
+    hipLaunchKernelGGL(ref_rows_kernel, dim3(cdiv(s, kRowsTile), groups), dim3(256), 0, st, mat, s, p0, cnt, rows, row_stride);
+    hipLaunchKernelGGL(ref_rows_tail_kernel, dim3(cdiv(cnt, 256)), dim3(256), 0, st, mat, s, p0, cnt, exc_g, exc_h, n_exc, rows, row_stride, len);
 }
 void launch_unpad_rows(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, u32 n_real, const u32* real2pad, u32* out) {
     if (n_rows == 0 || n_real == 0) return;

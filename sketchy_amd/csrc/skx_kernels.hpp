@@ -368,6 +368,15 @@ void launch_shared_debug(hipStream_t st, const u32* pair_q, const u32* poff, u32
 // 1 <= top_k <= min(kRowTopkMax, smallest species)
 constexpr u32 kRowTopkMax = 64;
 void launch_row_topk(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, const Species& sp, u32 top_k, u32 bound, u32* top_idx, u32* top_val);
+// the same for rows ranked in ONE species with one genome each left out (skx_ref_neighbours): row r = the first top_k genomes of `species`
+// other than excl0 + r; top_idx / top_val [n_rows][top_k]; 1 <= top_k <= min(kRowTopkMax, genomes of the species - 1)
+void launch_row_topk_excl(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, const Species& sp, u32 species, u32 excl0, u32 top_k, u32 bound,
+                          u32* top_idx, u32* top_val);
+// genomes [p0, p0 + cnt) (padded indices) of the resident matrix [n_tiles][s][256] as query rows [cnt][row_stride] (row_stride >= s):
+// ascending, zero-padded, the genome's lifted hashes (exc_g ascending, a genome's hashes descending) appended in ascending order;
+// len [cnt] = entries of each row.  Two launches on st.
+void launch_ref_rows(hipStream_t st, const u64* mat, u32 s, u32 p0, u32 cnt, const u32* exc_g, const u64* exc_h, u32 n_exc, u64* rows,
+                     u32 row_stride, u32* len);
 // out[n_rows][n_real] = cnt[row][real2pad[g]]
 void launch_unpad_rows(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, u32 n_real, const u32* real2pad, u32* out);
 void launch_add_table(hipStream_t st, u64* cum, const u64* add, u32 n_real, const u32* real2pad);

@@ -61,6 +61,9 @@ extern "C" int skx_rank_sketches(const skx_ref* ref, const uint64_t* query, cons
 extern "C" int skx_ref_set_genotypes(skx_ref* ref, uint32_t n_features, const uint32_t* codes) __attribute__((weak));
 extern "C" int skx_consensus_rows(const skx_ref* ref, const uint32_t* idx, uint64_t n_rows, uint32_t top_k, uint32_t* codes_out) __attribute__((weak));
 extern "C" int skx_stream_bind_consensus(skx_stream* st, uint32_t* codes_out) __attribute__((weak));
+// ... and the leave-one-out neighbours of the resident reference (`neighbours`): without it the host intersects the file's sketches itself.
+extern "C" int skx_ref_neighbours(const skx_ref* ref, uint32_t species, uint32_t first, uint32_t count, uint32_t top_k, uint32_t* nb_idx,
+                                  uint32_t* nb_shared, uint32_t* codes_out) __attribute__((weak));
 // ... and the per-batch event list (`predict -s --changes`): without it the host finds the change points itself, over every read's rows.
 extern "C" int skx_stream_bind_changes(skx_stream* st, uint32_t cap, uint32_t* n_events, uint32_t* ev_read, uint32_t* ev_idx, uint64_t* ev_sum,
                                        uint32_t* ev_codes) __attribute__((weak));
@@ -74,6 +77,11 @@ struct PredictConfig { size_t top = 1, limit = 0; bool stream = false, consensus
                        size_t threads = 0; bool timing = false, pin = false; };
 
 struct SketchyError : std::runtime_error { using std::runtime_error::runtime_error; };
+// a command line that asks for something the inputs cannot give (found only once they are read): exit status 2, as usage errors
+struct UsageError : SketchyError { using SketchyError::SketchyError; };
+
+// (not in the reference) `neighbours`: rows, one consensus line per genome, or one line per genotype column
+struct NeighboursConfig { size_t top = 1; bool consensus = false, summary = false, header = false; };
 
 static void hip_check(int rc, const char* what) {
     if (rc != SKX_OK) throw SketchyError(std::string(what) + ": " + skx_last_error());
@@ -134,6 +142,81 @@ class Sketchy {
         const auto geno = read_genotypes(genotypes);
         if (sk.size() != geno.rows) throw SketchyError("reference sketch and genotype table must have the same length");
         out << "ok\n";
+    }
+
+    // `neighbours` (not in the reference; the question of its "Sketch validation" section asked directly): for every sketch of the file,
+    // in file order, the `top` OTHER sketches that share the most hashes with it -- (shared desc, file order asc), what offline predict of
+    // the genome's own sketch prints against a reference that lacks it -- as rows, as one consensus line per genome (-c), or as one
+    // "column correct total" line per genotype column (-S): correct = genomes whose own string is the consensus of their neighbours.
+    // The rows (and with a genotype table the consensus codes) come from skx_ref_neighbours.  A library without it (tests/stub) has no
+    // counts to give either -- the host then intersects the file's sketches itself (src/sketchy.rs:425-438, all pairs: for files of test
+    // size), sorts stably with the genome itself skipped and votes over the rows as print_results does.  Both ways print the same bytes.
+    void neighbours(const std::string& reference, const std::string& genotypes, const NeighboursConfig& config, std::ostream& out) {
+        const auto sketches = read_sketch(reference);
+        const size_t n = sketches.size(), top = config.top;
+        if (n < 2) throw SketchyError("neighbours needs a reference of at least two sketches");
+        if (top < 1 || top > n - 1) throw UsageError("--top must be between 1 and the number of reference sketches - 1 = " + std::to_string(n - 1));
+        const bool with_geno = !genotypes.empty();
+        Genotypes geno;
+        if (with_geno) {
+            geno = read_genotypes(genotypes);
+            for (const auto& s : sketches)
+                if (!geno.map.count(s.name)) throw SketchyError("reference sketch " + s.name + " has no row in the genotype table");
+        }
+        Ref ref(sketches, device_);
+        std::vector<uint32_t> idx(n * top), shared(n * top), codes;
+        cons_ = ConsensusTable();
+        const bool want_call = config.consensus || config.summary;
+        if (skx_ref_neighbours && top <= SKX_MAX_TOP) {
+            if (want_call) { PredictConfig pc; pc.top = top; set_consensus_table(sketches, ref, geno, pc); }
+            if (cons_.on) codes.resize(n * cons_.nfeat);
+            hip_check(skx_ref_neighbours(ref.h, 0, 0, (uint32_t)n, (uint32_t)top, idx.data(), shared.data(), cons_.on ? codes.data() : nullptr), "neighbours");
+        } else {
+            std::vector<uint32_t> common(n), order;
+            for (size_t g = 0; g < n; ++g) {
+                const auto& a = sketches[g].hashes;
+                order.clear();
+                for (size_t h = 0; h < n; ++h) {
+                    const auto& b = sketches[h].hashes;
+                    uint32_t c = 0;
+                    for (size_t i = 0, j = 0; i < a.size() && j < b.size();) {
+                        if (a[i] < b[j]) ++i; else if (b[j] < a[i]) ++j; else { ++c; ++i; ++j; }
+                    }
+                    common[h] = c;
+                    if (h != g) order.push_back((uint32_t)h);
+                }
+                std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return common[x] > common[y]; });
+                for (size_t j = 0; j < top; ++j) { idx[g * top + j] = order[j]; shared[g * top + j] = common[order[j]]; }
+            }
+        }
+        // the call of genome g's neighbours, one string per genotype column
+        auto call_of = [&](size_t g) {
+            if (!cons_.on) return vote(sketches, geno, idx.data() + g * top, top);
+            std::vector<std::string> call;
+            for (size_t j = 0; j < cons_.nfeat; ++j) call.push_back(cons_.values[j][codes[g * cons_.nfeat + j]]);
+            return call;
+        };
+        if (config.summary) {
+            const auto columns = split_tab(geno.header);
+            std::vector<size_t> correct(columns.size(), 0);
+            for (size_t g = 0; g < n; ++g) {
+                const auto call = call_of(g);
+                const auto& own = geno.map.at(sketches[g].name);
+                for (size_t j = 0; j < columns.size(); ++j) correct[j] += j < call.size() && j < own.size() && call[j] == own[j] ? 1 : 0;
+            }
+            for (size_t j = 0; j < columns.size(); ++j) out << columns[j] << "\t" << correct[j] << "\t" << n << "\n";
+            return;
+        }
+        if (config.header) out << "sketch_id\tneighbour_id\tshared_hashes" << (with_geno ? "\t" + geno.header : std::string()) << "\n";
+        for (size_t g = 0; g < n; ++g) {
+            if (config.consensus) { out << sketches[g].name << "\t-\t-\t" << join_tab(call_of(g)) << "\n"; continue; }
+            for (size_t j = 0; j < top; ++j) {
+                const auto& name = sketches[idx[g * top + j]].name;
+                out << sketches[g].name << "\t" << name << "\t" << shared[g * top + j];
+                if (with_geno) out << "\t" << join_tab(geno.map.at(name));
+                out << "\n";
+            }
+        }
     }
 
     void info(const std::string& input, bool params, std::ostream& out) {
@@ -943,19 +1026,24 @@ class Sketchy {
         }
     }
 
+    // the consensus branch's vote (src/sketchy.rs:365-388) over one row of `top` genomes: per genotype column the string most of them carry
+    static std::vector<std::string> vote(const std::vector<Sketch>& sketches, const Genotypes& geno, const uint32_t* idx, size_t top) {
+        const size_t nfeat = geno.map.at(sketches[idx[0]].name).size();
+        std::vector<std::string> call;
+        for (size_t j = 0; j < nfeat; ++j) {
+            std::map<std::string, size_t> counts;  // ties: the reference's HashMap order is unspecified; here: smallest value
+            for (size_t t = 0; t < top; ++t) counts[geno.map.at(sketches[idx[t]].name)[j]]++;
+            auto best = std::max_element(counts.begin(), counts.end(), [](const auto& a, const auto& b) { return a.second < b.second; });
+            call.push_back(best->first);
+        }
+        return call;
+    }
+
     // src/sketchy.rs:358-402
     void print_results(const std::vector<Sketch>& sketches, const Genotypes& geno, const uint32_t* idx, const uint64_t* sum,
                        size_t read, const PredictConfig& config, std::ostream& out) {
         if (config.consensus) {
-            const size_t nfeat = geno.map.at(sketches[idx[0]].name).size();
-            std::vector<std::string> call;
-            for (size_t j = 0; j < nfeat; ++j) {
-                std::map<std::string, size_t> counts;  // ties: the reference's HashMap order is unspecified; here: smallest value
-                for (size_t t = 0; t < config.top; ++t) counts[geno.map.at(sketches[idx[t]].name)[j]]++;
-                auto best = std::max_element(counts.begin(), counts.end(), [](const auto& a, const auto& b) { return a.second < b.second; });
-                call.push_back(best->first);
-            }
-            out << read << "\t-\t-\t" << join_tab(call) << "\n";
+            out << read << "\t-\t-\t" << join_tab(vote(sketches, geno, idx, config.top)) << "\n";
         } else {
             for (size_t t = 0; t < config.top; ++t) {
                 const auto& name = sketches[idx[t]].name;
@@ -977,6 +1065,11 @@ static void usage() {
                  "sketchy-hip predict -r REF.msh -g GENO.tsv [-i READS.fx[.gz] ...] [-t TOP] [-l LIMIT] [-s] [-c] [-H] [-x] [-b BATCH_READS] [-j THREADS] [--timing] [--pin]\n"
                  "                    (without -s: several inputs, one sample each -- the rows of every sample in input order; -l per input; -s: one input;\n"
                  "                    -x / --changes, with -s: only read 1 and the reads whose lines, the shared_hashes column aside, differ from the read before)\n"
+                 "sketchy-hip neighbours -r REF.msh [-g GENO.tsv] [-t TOP=1] [-c] [-S] [-H]\n"
+                 "                    (leave-one-out: per sketch of REF, in file order, the TOP other sketches that share the most hashes with it --\n"
+                 "                    sketch_id neighbour_id shared_hashes [the neighbour's genotype columns]; -c, with -g and an odd TOP: one line per\n"
+                 "                    sketch, the consensus of its neighbours; -S / --summary, with -g: one line per genotype column -- column, the\n"
+                 "                    sketches whose own value is that consensus, all sketches)\n"
                  "sketchy-hip shared  -r REF.msh -q QUERY.msh\n"
                  "sketchy-hip info    -i SKETCH.msh [-p]\n"
                  "sketchy-hip check   -r REF.msh -g GENO.tsv\n");
@@ -990,7 +1083,7 @@ int main(int argc, char** argv) {
     const std::map<std::string, std::string> longnames = {{"--input", "-i"}, {"--reference", "-r"}, {"--genotypes", "-g"}, {"--top", "-t"}, {"--limit", "-l"},
                                                           {"--stream", "-s"}, {"--consensus", "-c"}, {"--header", "-H"}, {"--query", "-q"}, {"--params", "-p"},
                                                           {"--device", "-d"}, {"--batch", "-b"}, {"--output", "-o"}, {"--sketch-size", "-s"},
-                                                          {"--kmer-size", "-k"}, {"--seed", "-e"}, {"--threads", "-j"}, {"--timing", "-T"}, {"--pin", "-P"}, {"--counts", "-C"}, {"--changes", "-x"}};
+                                                          {"--kmer-size", "-k"}, {"--seed", "-e"}, {"--threads", "-j"}, {"--timing", "-T"}, {"--pin", "-P"}, {"--counts", "-C"}, {"--changes", "-x"}, {"--summary", "-S"}};
     const bool is_sketch = cmd == "sketch";  // there -s takes a value (sketch size), elsewhere it is --stream
     const bool many_inputs = is_sketch || cmd == "predict";
     for (int i = 2; i < argc; ++i) {
@@ -999,7 +1092,7 @@ int main(int argc, char** argv) {
         if (longnames.count(a)) a = longnames.at(a);
         // (predict: a lone "-" is a path -- stdin)
         if (many_inputs && a == "-i") { while (i + 1 < argc && (argv[i + 1][0] != '-' || (!is_sketch && !argv[i + 1][1]))) inputs.push_back(argv[++i]); continue; }
-        if ((!is_sketch && a == "-s") || a == "-c" || a == "-H" || a == "-p" || a == "-T" || a == "-P" || a == "-C" || a == "-x") flag[a] = true;
+        if ((!is_sketch && a == "-s") || a == "-c" || a == "-H" || a == "-p" || a == "-T" || a == "-P" || a == "-C" || a == "-x" || a == "-S") flag[a] = true;
         else if (i + 1 < argc) opt[a] = argv[++i];
         else { usage(); return 2; }
     }
@@ -1033,6 +1126,22 @@ int main(int argc, char** argv) {
             cfg.stream = flag["-s"]; cfg.consensus = flag["-c"]; cfg.header = flag["-H"]; cfg.changes = flag["-x"];
             cfg.threads = opt.count("-j") ? (size_t)std::max(1L, std::atol(opt["-j"].c_str())) : 0; cfg.timing = flag["-T"]; cfg.pin = flag["-P"];
             app.predict(inputs, opt["-r"], opt["-g"], cfg, std::cout);
+        } else if (cmd == "neighbours") {
+            if (!opt.count("-r")) { usage(); return 2; }
+            sketchy::NeighboursConfig cfg;
+            const long top = opt.count("-t") ? std::atol(opt["-t"].c_str()) : 1;
+            cfg.consensus = flag["-c"]; cfg.summary = flag["-S"]; cfg.header = flag["-H"];
+            if (top < 1) { std::fprintf(stderr, "Error: --top must be at least 1\n"); return 2; }
+            if ((cfg.consensus || cfg.summary) && !opt.count("-g")) {
+                std::fprintf(stderr, "Error: neighbours --consensus / --summary call genotypes: they need -g\n");
+                return 2;
+            }
+            if (cfg.consensus && top % 2 != 1) {  // (the rule of predict -c, src/sketchy.rs:74-79)
+                std::fprintf(stderr, "Error: --top must be an odd number when using --consensus\n");
+                return 2;
+            }
+            cfg.top = (size_t)top;
+            app.neighbours(opt["-r"], opt.count("-g") ? opt["-g"] : std::string(), cfg, std::cout);
         } else if (cmd == "shared") {
             if (!opt.count("-r") || !opt.count("-q")) { usage(); return 2; }
             app.shared(opt["-r"], opt["-q"], std::cout);
@@ -1043,6 +1152,9 @@ int main(int argc, char** argv) {
             if (!opt.count("-i")) { usage(); return 2; }
             app.info(opt["-i"], flag["-p"], std::cout);
         } else { usage(); return 2; }
+    } catch (const sketchy::UsageError& e) {
+        std::fprintf(stderr, "Error: %s\n", e.what());
+        return 2;
     } catch (const std::exception& e) {
         std::fprintf(stderr, "Error: %s\n", e.what());
         return 1;

@@ -25,6 +25,8 @@
  *   skx_predict_groups     <- all of Sketchy::_shared_hashes (src/sketchy.rs:281-315) for many samples: pool, count, rank
  *   skx_stream_bind_changes / skx_changes_rows <- no counterpart: the reference prints every read's rows (:348-349, :391-399); these
  *                             report only the reads at which what it would print (indices or consensus) differs from the read before
+ *   skx_stream_bind_call / skx_stream_bind_call_changes / skx_call_rows <- no counterpart: the reference ranks against one file; these
+ *                             say which of the resident species the sample is after every read, with that species' rows alone
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
  *   skx_sketch_groups      <- finch SketchScheme::{process x many, to_vec}: ONE sketcher fed several records -- all reads of an
  *                             offline `predict` (src/sketchy.rs:291-302), all contigs of a genome file in `sketch` (:473-478)
@@ -332,6 +334,51 @@ int skx_stream_bind_consensus(skx_stream *st, uint32_t *codes_out);
  */
 int skx_stream_bind_changes(skx_stream *st, uint32_t cap, uint32_t *n_events, uint32_t *ev_read, uint32_t *ev_idx, uint64_t *ev_sum,
                             uint32_t *ev_codes);
+/*
+ * Species call of a batch: for a reference of several species, which species the sample is after every read, and that species' rows
+ * alone.  (The reference binary ranks against one file; a sample of unknown species is run once per file and the outputs are compared.)
+ * For a stream with top_k >= 1 over a reference of n_species >= 1, after read r of a batch:
+ *   lead[r][sp] = topk_sum[r][sp][0], the running sum of species sp's best genome.  All species share s, so the sums are comparable;
+ *                 nothing is normalised.
+ *   c(r)        = the SMALLEST sp whose lead[r][sp] is the maximum over the species: a table of zeros calls species 0, and two species
+ *                 holding the same genomes call the lower one.
+ *   call(r)     = (c(r), topk_idx[r][c(r)][0..top_k), topk_sum[r][c(r)][0..top_k)) and, with a genotype table, the consensus codes
+ *                 [n_features] of species c(r) (skx_ref_set_genotypes: meaning, tie rule).
+ * skx_stream_bind_call binds, for the NEXT batch handed to skx_stream_push, _push_device, _enqueue_device or _submit (ONE-SHOT, consumed
+ * by that call whether it succeeds or fails, like skx_stream_bind_consensus):
+ *   call_species [n_reads]              c(r); required
+ *   call_idx     [n_reads][top_k]       optional: the called species' index row (genome indices local to that species)
+ *   call_sum     [n_reads][top_k]       optional: its sums
+ *   call_codes   [n_reads][n_features]  optional: its consensus codes
+ * skx_stream_bind_call_changes binds, likewise, the CALL CHANGE POINTS of the batch: read r is one iff r == 0, or c(r) != c(r - 1), or the
+ * compared part of the call differs in any element -- the index row, or in codes mode (ev_codes != NULL) the codes; sums are never
+ * compared.  STATELESS PER BATCH exactly as skx_stream_bind_changes: read 0 of every batch is an event, nothing is carried across
+ * batches on the device, the caller compares a batch's first event with the last call it kept.
+ *   n_events   [1]                  call change points of the batch, NOT capped; required
+ *   ev_read    [cap]                batch-local read ordinals, ascending; required
+ *   ev_species [cap]                c of those reads; required
+ *   ev_idx     [cap][top_k]         optional: their index rows
+ *   ev_sum     [cap][top_k]         optional: their sums
+ *   ev_codes   [cap][n_features]    optional: their codes; non-NULL selects codes mode
+ * The first min(n_events, cap) entries are written, nothing else is touched.  An empty batch gives n_events = 0.
+ * The two bindings are independent of each other and of the consensus and changes bindings: a batch may have all four.  Output memory
+ * is the kind the entry point's other outputs are (host / device / page-locked host) and valid whenever that call's rows are.  With a
+ * call bound, skx_stream_push and skx_stream_submit may be given NULL for topk_idx and topk_sum: then only the call travels back,
+ * 1 + top_k values per read instead of n_species x top_k.
+ * A bound batch call fails with SKX_ERR_INVALID, before any device work and with the binding consumed, when the stream has top_k == 0,
+ * when call_codes or ev_codes is given and the reference has no genotype table, or when a _device entry point is given
+ * d_topk_idx == NULL or d_topk_sum == NULL (the lead needs the sums, and the stream's fallback rows are shared between chains).
+ * NULL stream, NULL required pointer, cap == 0: SKX_ERR_INVALID here.
+ * Selected on the device behind the ranking, on the queue that ranked the batch, once its rows are final (and voted on, when codes
+ * are wanted; the vote goes to the scratch the consensus binding uses): one kernel per pass writes the species, the compact rows and a
+ * compare key {species, index row | codes}; the events are the change points of that key (flags, scan, gather: DESIGN.md 4).
+ * Scratch -- compact rows, key, flags and positions, event arrays; per stream for pushes, per staging slot for submits -- is allocated
+ * by the first bound batch; a stream that never binds launches nothing and allocates nothing for this, and its rows and table are what
+ * they were.
+ */
+int skx_stream_bind_call(skx_stream *st, uint32_t *call_species, uint32_t *call_idx, uint64_t *call_sum, uint32_t *call_codes);
+int skx_stream_bind_call_changes(skx_stream *st, uint32_t cap, uint32_t *n_events, uint32_t *ev_read, uint32_t *ev_species,
+                                 uint32_t *ev_idx, uint64_t *ev_sum, uint32_t *ev_codes);
 /* running sum-of-shared-hashes table, u64[n_genomes] (host) */
 int skx_stream_table(skx_stream *st, uint64_t *cum);
 /*
@@ -464,6 +511,16 @@ int skx_ref_neighbours(const skx_ref *ref, uint32_t species, uint32_t first, uin
  * before the device is touched.  n_rows == 0: SKX_OK, n_events = 0. */
 int skx_changes_rows(int device, const uint32_t *rows, uint64_t n_rows, uint32_t width, uint64_t cap, uint64_t *n_events,
                      uint64_t *ev_row);
+
+/* The species call (skx_stream_bind_call: definitions, tie rule) alone on rows the caller holds (host): idx / sum
+ * [n_rows][n_species][top_k], codes [n_rows][n_species][n_features] or NULL.  call_species [n_rows] receives c(r); call_idx / call_sum
+ * [n_rows][top_k] and call_codes [n_rows][n_features], each optional, the called species' rows.  Works in chunks: at most 64 MiB of
+ * input rows are on the device at a time.  All found before the device is touched, SKX_ERR_INVALID: NULL idx, sum or call_species;
+ * n_species outside 1..SKX_MAX_SPECIES; top_k outside 1..SKX_MAX_TOP; exactly one of codes and call_codes; n_features outside
+ * 1..SKX_MAX_FEATURES when codes is given.  n_rows == 0: SKX_OK, nothing is touched. */
+int skx_call_rows(int device, const uint32_t *idx, const uint64_t *sum, const uint32_t *codes, uint64_t n_rows, uint32_t n_species,
+                  uint32_t top_k, uint32_t n_features, uint32_t *call_species, uint32_t *call_idx, uint64_t *call_sum,
+                  uint32_t *call_codes);
 
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI --------------------------------- */
 #define SKX_COMM_ID_BYTES 128

@@ -60,6 +60,8 @@ SYMBOLS = [
     ("skx_stream_drain", _i, [_vp]),
     ("skx_stream_bind_consensus", _i, [_vp, _vp]),
     ("skx_stream_bind_changes", _i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    ("skx_stream_bind_call", _i, [_vp, _vp, _vp, _vp, _vp]),
+    ("skx_stream_bind_call_changes", _i, [_vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("skx_stream_table", _i, [_vp, _vp]),
     ("skx_stream_table_add", _i, [_vp, _vp]),
     ("skx_stream_reset", _i, [_vp]),
@@ -78,6 +80,7 @@ SYMBOLS = [
     ("skx_consensus_rows", _i, [_vp, _vp, _u64, _u32, _vp]),
     ("skx_ref_neighbours", _i, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp]),
     ("skx_changes_rows", _i, [_i, _vp, _u64, _u32, _u64, C.POINTER(_u64), _vp]),
+    ("skx_call_rows", _i, [_i, _vp, _vp, _vp, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
     ("skx_predict_groups", _i, [_vp, _vp, _vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("skx_comm_unique_id", _i, [_vp]),
     ("skx_comm_create", _i, [_pp, _i, _i, _i, _vp]),

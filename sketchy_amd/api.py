@@ -304,14 +304,34 @@ class SumOfSharedHashes:
         ev_read [cap], ev_idx / ev_sum [cap, n_species, top], ev_codes [cap, n_species, F] (not None: codes mode)."""
         _lib.check(_lib.load().skx_stream_bind_changes(self._h, cap, n_events, ev_read, ev_idx, ev_sum, ev_codes))
 
-    def _bind(self, consensus, changes):
+    def bind_call(self, call_species, call_idx=None, call_sum=None, call_codes=None):
+        """Bind a species call (pointers / addresses; skx_stream_bind_call) for the NEXT batch call, which consumes it:
+        call_species [n_reads], call_idx / call_sum [n_reads, top], call_codes [n_reads, F]."""
+        _lib.check(_lib.load().skx_stream_bind_call(self._h, call_species, call_idx, call_sum, call_codes))
+
+    def bind_call_changes(self, cap, n_events, ev_read, ev_species, ev_idx=None, ev_sum=None, ev_codes=None):
+        """Bind the call's event list (pointers / addresses; skx_stream_bind_call_changes) for the NEXT batch call, which consumes it:
+        n_events [1], ev_read / ev_species [cap], ev_idx / ev_sum [cap, top], ev_codes [cap, F] (not None: codes mode)."""
+        _lib.check(_lib.load().skx_stream_bind_call_changes(self._h, cap, n_events, ev_read, ev_species, ev_idx, ev_sum, ev_codes))
+
+    def _bind(self, consensus, changes, call=None, call_changes=None):
         if consensus is not None:
             self.bind_consensus(consensus)
         if changes is not None:
             self.bind_changes(*changes)
+        if call is not None:
+            self.bind_call(*call)
+        if call_changes is not None:
+            self.bind_call_changes(*call_changes)
 
-    def push(self, bases, offsets, want_shared=False, want_sketches=False, want_consensus=False, want_changes=None, changes_codes=False):
-        """Consume a packed batch; returns dict(topk_idx, topk_sum[, shared, sketches, sketch_len, consensus, changes]).
+    def push(self, bases, offsets, want_shared=False, want_sketches=False, want_consensus=False, want_changes=None, changes_codes=False,
+             want_call=False, want_call_changes=0, call_changes_codes=False):
+        """Consume a packed batch; returns dict(topk_idx, topk_sum[, shared, sketches, sketch_len, consensus, changes, call_*]).
+        want_call: also the species call of every read (skx_stream_bind_call) -- out["call_species"] [n_reads]: the lowest species
+        whose leader has the largest sum; out["call_idx"], out["call_sum"] [n_reads, top]: that species' rows; out["call_codes"]
+        [n_reads, F]: its consensus codes (None without a genotype table).  want_call_changes=cap (0: none): the reads at which the
+        call changes -- species or index row (call_changes_codes: species or codes), read 0 always among them -- as out["call_events"]
+        = dict(n_events, read, species, idx, sum[, codes]): n_events not capped, the arrays the first min(n_events, cap) entries.
         want_changes=cap: also the batch's change points -- the reads whose index row (changes_codes: whose consensus codes) differs
         from the previous read's, read 0 always among them -- as out["changes"] = dict(n, read, idx, sum[, codes]): n their number
         (not capped), the arrays the first min(n, cap) of them.  Rows are
@@ -340,8 +360,26 @@ class SumOfSharedHashes:
             ev_idx, ev_sum = np.zeros((cap,) + shape[1:], np.uint32), np.zeros((cap,) + shape[1:], np.uint64)
             ev_codes = np.zeros((cap,) + shape[1:-1] + (self.ref.n_features,), np.uint32) if changes_codes else None
             self.bind_changes(cap, _p(ev_n), _p(ev_read), _p(ev_idx), _p(ev_sum), _p(ev_codes))
+        nf = self.ref.n_features if (want_call or want_call_changes) else 0
+        if want_call:
+            c_sp, c_idx, c_sum = np.zeros(n, np.uint32), np.zeros((n, self.top), np.uint32), np.zeros((n, self.top), np.uint64)
+            c_codes = np.zeros((n, nf), np.uint32) if nf else None
+            self.bind_call(_p(c_sp), _p(c_idx), _p(c_sum), _p(c_codes))
+        if want_call_changes:
+            ccap = int(want_call_changes)
+            cev_n, cev_read, cev_sp = np.zeros(1, np.uint32), np.zeros(ccap, np.uint32), np.zeros(ccap, np.uint32)
+            cev_idx, cev_sum = np.zeros((ccap, self.top), np.uint32), np.zeros((ccap, self.top), np.uint64)
+            cev_codes = np.zeros((ccap, nf), np.uint32) if call_changes_codes else None
+            self.bind_call_changes(ccap, _p(cev_n), _p(cev_read), _p(cev_sp), _p(cev_idx), _p(cev_sum), _p(cev_codes))
         _lib.check(L.skx_stream_push(self._h, _p(b), _p(offsets), n, _p(ti), _p(ts), _p(sh), _p(sk), _p(sl)))
         out.update(topk_idx=ti, topk_sum=ts, shared=sh, sketches=sk, sketch_len=sl)
+        if want_call:
+            out.update(call_species=c_sp, call_idx=c_idx, call_sum=c_sum, call_codes=c_codes)
+        if want_call_changes:
+            m = min(int(cev_n[0]), ccap)
+            out["call_events"] = dict(n_events=int(cev_n[0]), read=cev_read[:m], species=cev_sp[:m], idx=cev_idx[:m], sum=cev_sum[:m])
+            if call_changes_codes:
+                out["call_events"]["codes"] = cev_codes[:m]
         if want_consensus:
             out["consensus"] = cons
         if want_changes is not None:
@@ -351,16 +389,21 @@ class SumOfSharedHashes:
                 out["changes"]["codes"] = ev_codes[:m]
         return out
 
-    def push_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None, changes=None):
+    def push_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None, changes=None,
+                    call=None, call_changes=None):
         """consensus: device pointer for the batch's consensus codes, bound right before the call (needs d_topk_idx);
-        changes: (cap, n_events, ev_read[, ev_idx, ev_sum, ev_codes]) device pointers of an event list (bind_changes), likewise"""
-        self._bind(consensus, changes)
+        changes: (cap, n_events, ev_read[, ev_idx, ev_sum, ev_codes]) device pointers of an event list (bind_changes), likewise;
+        call: (call_species[, call_idx, call_sum, call_codes]) device pointers of a species call (bind_call), and call_changes:
+        (cap, n_events, ev_read, ev_species[, ev_idx, ev_sum, ev_codes]) of its event list (bind_call_changes), likewise (both need
+        d_topk_idx and d_topk_sum)"""
+        self._bind(consensus, changes, call, call_changes)
         _lib.check(_lib.load().skx_stream_push_device(self._h, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum))
 
-    def enqueue_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None, changes=None):
+    def enqueue_device(self, d_bases, d_offsets, n_reads, n_bases, d_topk_idx=None, d_topk_sum=None, consensus=None, changes=None,
+                       call=None, call_changes=None):
         """push_device with the host wait of batch i overlapped by the sketch of batch i + 1: the passes (and any
         error) of a batch are queued by the NEXT enqueue / flush / sync.  Same rows, same table."""
-        self._bind(consensus, changes)
+        self._bind(consensus, changes, call, call_changes)
         _lib.check(_lib.load().skx_stream_enqueue_device(self._h, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum))
 
     def flush(self):
@@ -373,12 +416,15 @@ class SumOfSharedHashes:
     def sync(self):
         _lib.check(_lib.load().skx_stream_sync(self._h))
 
-    def submit(self, h_bases, h_offsets, n_reads, h_topk_idx=None, h_topk_sum=None, consensus=None, changes=None) -> int:
+    def submit(self, h_bases, h_offsets, n_reads, h_topk_idx=None, h_topk_sum=None, consensus=None, changes=None,
+               call=None, call_changes=None) -> int:
         """Queue a batch held in page-locked host memory (HostBuffer pointers / addresses); returns its ticket.  The
         copy overlaps the previous batch's kernels; rows are valid after wait(ticket) or drain().  consensus: page-locked
         pointer for the batch's consensus codes, bound right before the call; the row pointers may then be None.  changes:
-        (cap, n_events, ev_read[, ev_idx, ev_sum, ev_codes]) page-locked pointers of an event list (bind_changes), likewise."""
-        self._bind(consensus, changes)
+        (cap, n_events, ev_read[, ev_idx, ev_sum, ev_codes]) page-locked pointers of an event list (bind_changes), likewise.
+        call: (call_species[, call_idx, call_sum, call_codes]) and call_changes: (cap, n_events, ev_read, ev_species[, ev_idx, ev_sum,
+        ev_codes]) page-locked pointers of a species call and its event list (bind_call, bind_call_changes), likewise."""
+        self._bind(consensus, changes, call, call_changes)
         t = C.c_uint64(0)
         _lib.check(_lib.load().skx_stream_submit(self._h, h_bases, h_offsets, n_reads, h_topk_idx, h_topk_sum, C.byref(t)))
         return t.value
@@ -500,6 +546,31 @@ def changes_rows(rows, cap=None, device=0):
     src = rows if rows.size else np.zeros(1, np.uint32)
     _lib.check(_lib.load().skx_changes_rows(device, _p(src), n, width, cap, C.byref(n_ev), _p(ev)))
     return n_ev.value, ev[:min(n_ev.value, cap)]
+
+
+def call_rows(idx, sums, codes=None, device=0):
+    """Species call of rows held on the host (skx_call_rows): idx uint32 / sums uint64 [n, n_species, top], codes uint32
+    [n, n_species, F] or None.  Returns dict(call_species [n], call_idx, call_sum [n, top], call_codes [n, F] or None): per row the
+    lowest species whose leader sums[r, sp, 0] is the largest, and that species' rows."""
+    idx = np.ascontiguousarray(idx, np.uint32)
+    sums = np.ascontiguousarray(sums, np.uint64)
+    if idx.ndim != 3 or idx.shape != sums.shape:
+        raise ValueError("idx and sums must both be [n_rows, n_species, top]")
+    n, n_sp, top = idx.shape
+    nf = 0
+    if codes is not None:
+        codes = np.ascontiguousarray(codes, np.uint32)
+        if codes.ndim != 3 or codes.shape[:2] != (n, n_sp):
+            raise ValueError("codes must be [n_rows, n_species, n_features]")
+        nf = codes.shape[2]
+    c_sp, c_idx, c_sum = np.zeros(n, np.uint32), np.zeros((n, top), np.uint32), np.zeros((n, top), np.uint64)
+    c_codes = np.zeros((n, nf), np.uint32) if codes is not None else None
+    pad = lambda a, t: a if a.size else np.zeros(1, t)  # (an empty array has no address worth passing)
+    _lib.check(_lib.load().skx_call_rows(device, _p(pad(idx, np.uint32)), _p(pad(sums, np.uint64)),
+                                         _p(pad(codes, np.uint32)) if codes is not None else None, n, n_sp, top, nf,
+                                         _p(pad(c_sp, np.uint32)), _p(pad(c_idx, np.uint32)), _p(pad(c_sum, np.uint64)),
+                                         _p(pad(c_codes, np.uint32)) if codes is not None else None))
+    return dict(call_species=c_sp, call_idx=c_idx, call_sum=c_sum, call_codes=c_codes)
 
 
 def sketch_reads(bases, offsets, k=16, seed=0, s=1000, device=0):

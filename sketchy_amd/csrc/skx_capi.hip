@@ -929,6 +929,22 @@ struct ChangeOut {
     u32* ev_codes = nullptr;
     bool codes = false;  // the call of a read is its consensus codes, not its index row
 };
+// Species call of a batch (skx_stream_bind_call: on; skx_stream_bind_call_changes: cap != 0), travelling like ChangeOut: the caller's
+// arrays in skx_stream::bound_call, DEVICE arrays in a PendingBatch / SubPass.  Compact rows nobody asked for but the event list
+// needs go to the ranking lane's scratch.
+struct CallOut {
+    bool on = false;
+    u32 *sp = nullptr, *idx = nullptr;
+    u64* sum = nullptr;
+    u32* codes = nullptr;
+    u32 cap = 0;
+    u32 n_batch = 0;
+    u32 *n_events = nullptr, *ev_read = nullptr, *ev_sp = nullptr, *ev_idx = nullptr;
+    u64* ev_sum = nullptr;
+    u32* ev_codes = nullptr;  // non-NULL: the compared part of the call is its codes
+    bool any() const { return on || cap != 0; }
+    bool wants_codes() const { return codes != nullptr || ev_codes != nullptr; }
+};
 struct PendingBatch {
     bool valid = false;
     int side = 0;  // which copy of the sketch buffers holds it
@@ -956,6 +972,7 @@ struct PendingBatch {
     void* slot = nullptr;      // skx_stream::Staged of a host-fed batch: its rows travel to the host behind the ranking
     u32* d_cons = nullptr;     // [n_reads][n_species][n_features] consensus codes of its rows (skx_stream_bind_consensus) or NULL
     ChangeOut chg;             // its event list (skx_stream_bind_changes)
+    CallOut call;              // its species call (skx_stream_bind_call, skx_stream_bind_call_changes)
 };
 
 // The HIP streams of the pipeline, ONE set per device shared by every skx_stream on it.  Measured (tools/diag_second_stream.py,
@@ -994,6 +1011,7 @@ struct SubPass {
     void* slot = nullptr;         // host-fed batches: the staging slot whose rows go back to the host behind the ranking
     u32* d_cons = nullptr;        // consensus codes of the BATCH's rows (row 0 = the batch's first read) or NULL
     ChangeOut chg;                // the BATCH's event list: flags for [ra, rb) here, scan + gather when rb ends the batch
+    CallOut call;                 // the BATCH's species call: selection and flags for [ra, rb) here, scan + gather when rb ends the batch
 };
 static const int kSides = kGroupMax + 1;  // copies of the per-batch sketch outputs: the enqueued batches waiting for their shared pass + the one being sketched
                                           // (a stream uses stream_coalesce + 1 of them, allocated at first use)
@@ -1198,6 +1216,13 @@ struct skx_stream {
         // change points (skx_stream_bind_changes; allocated by the first bound batch the lane ranks): one flag and one position per read
         // of a batch, the scan's block totals, and -- codes mode of a _device entry point without a consensus output -- the codes voted on
         u32 *d_chg_flag = nullptr, *d_chg_pos = nullptr, *d_chg_bsum = nullptr, *d_chg_codes = nullptr;
+        // species call (skx_stream_bind_call, skx_stream_bind_call_changes; each allocated by the first bound batch that needs it): flag,
+        // position and key {species, index row | codes} per read for the event list, and the compact rows an event list gathers from
+        // when the batch's call itself was not bound or leaves them out
+        u32 *d_call_flag = nullptr, *d_call_pos = nullptr, *d_call_bsum = nullptr, *d_call_key = nullptr;
+        u32 *d_call_sp = nullptr, *d_call_idx = nullptr, *d_call_codes = nullptr;
+        u64* d_call_sum = nullptr;
+        u32 call_key_w = 0;  // words per read d_call_key has room for: it grows when a wider key arrives (a genotype table set after the first rows-mode list)
         hipEvent_t ev_cum = nullptr;   // its chain's chunk_prefix is done: the table the NEXT batch starts from is complete
         hipEvent_t ev_done = nullptr;  // its chain is done
         bool ready = false;
@@ -1222,6 +1247,11 @@ struct skx_stream {
     // gathers into (d_ev: {n_events, ev_read, ev_idx, ev_sum, ev_codes} for d_ev.cap entries; grows with the caps asked for)
     ChangeOut bound_chg;
     ChangeOut d_ev;
+    // species call (skx_stream_bind_call, skx_stream_bind_call_changes): the arrays bound for the next batch call, and the device copy a
+    // bound skx_stream_push selects and gathers into (rows for max_reads reads, events for d_call.cap entries; each array allocated
+    // by the first push that asks for it)
+    CallOut bound_call;
+    CallOut d_call;
     u64* d_tab_tmp = nullptr;   // [n_genomes] staging of skx_stream_table / skx_stream_table_add
     u32* d_rank_idx = nullptr;  // [n_species][top] outputs of skx_stream_rank
     u64* d_rank_sum = nullptr;
@@ -1271,6 +1301,9 @@ struct skx_stream {
         ChangeOut out_chg;          // event list of the batch (the caller's page-locked arrays) or cap == 0; d_ev: the slot's device copy
         ChangeOut d_ev;             // (allocated by the slot's first bound submit, grows with the caps asked for); h_ev_n: page-locked, the
         u32* h_ev_n = nullptr;      // batch's n_events on its way back -- the host copies min(n_events, cap) entries once it is there
+        CallOut out_call;           // species call of the batch (the caller's page-locked arrays), d_call: the slot's device copy,
+        CallOut d_call;             // h_cev_n: its n_events on the way back -- as out_chg, d_ev and h_ev_n
+        u32* h_cev_n = nullptr;
         u32* d_rows_idx = nullptr;  // the slot's own device rows (batches may share a pass: each needs its rows until they are copied out)
         u64* d_rows_sum = nullptr;
         uint8_t* d_bases = nullptr;
@@ -1295,6 +1328,11 @@ struct skx_stream {
 
 static void free_side(skx_stream* st, int i);
 static void free_lane(skx_stream* st, int i);
+static void free_call(CallOut& d) {
+    void* ptrs[] = {d.sp, d.idx, d.sum, d.codes, d.n_events, d.ev_read, d.ev_sp, d.ev_idx, d.ev_sum, d.ev_codes};
+    for (void* q : ptrs) (void)hipFree(q);
+    d = CallOut{};
+}
 static void stream_free(skx_stream* st) {
     if (!st) return;
     (void)hipSetDevice(st->device);
@@ -1337,7 +1375,10 @@ static void stream_free(skx_stream* st) {
     (void)hipFree(st->d_ht[0]); (void)hipFree(st->d_ht[1]); (void)hipFree(st->d_dict_ctr[0]); (void)hipFree(st->d_dict_ctr[1]);
     (void)hipFree(st->d_slot_off); (void)hipFree(st->d_bcount); (void)hipFree(st->d_bbase);
     (void)hipFree(st->d_btot);
+    free_call(st->d_call);
     for (auto& sl : st->slot) {
+        free_call(sl.d_call);
+        if (sl.h_cev_n) (void)hipHostFree(sl.h_cev_n);
         (void)hipFree(sl.d_bases); (void)hipFree(sl.d_offsets); (void)hipFree(sl.d_rows_idx); (void)hipFree(sl.d_rows_sum); (void)hipFree(sl.d_cons);
         (void)hipFree(sl.d_ev.n_events); (void)hipFree(sl.d_ev.ev_read); (void)hipFree(sl.d_ev.ev_idx); (void)hipFree(sl.d_ev.ev_sum); (void)hipFree(sl.d_ev.ev_codes);
         if (sl.h_ev_n) (void)hipHostFree(sl.h_ev_n);
@@ -1489,7 +1530,8 @@ static void free_lane(skx_stream* st, int i) {
     skx_stream::RankLane& L = st->lane[i];
     void* ptrs[] = {L.d_inc, L.d_rel, L.d_live, L.d_has, L.d_lead_seg, L.d_live_ctr, L.d_csum, L.d_csum_raw, L.d_leader, L.d_lead_val,
                     L.d_lpart_sum, L.d_lpart_idx, L.d_gmax, L.d_cand_sum, L.d_cand_idx, L.d_cum_sink,
-                    L.d_chg_flag, L.d_chg_pos, L.d_chg_bsum, L.d_chg_codes};
+                    L.d_chg_flag, L.d_chg_pos, L.d_chg_bsum, L.d_chg_codes,
+                    L.d_call_flag, L.d_call_pos, L.d_call_bsum, L.d_call_key, L.d_call_sp, L.d_call_idx, L.d_call_codes, L.d_call_sum};
     for (void* q : ptrs) (void)hipFree(q);
     if (L.ev_cum) (void)hipEventDestroy(L.ev_cum);
     if (L.ev_done) (void)hipEventDestroy(L.ev_done);
@@ -2670,6 +2712,7 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
         if (sb.d_cons)  // the vote over the rows this sub-pass has just finished, behind the last kernel that writes them
             skx::launch_consensus_rows(ls, d_topk_idx, out_r0, n_reads, n_sp, st->top_k, ref->d_sp_g0, ref->d_codes, ref->n_features,
                                        sb.d_cons, n_pad);
+        u32* d_vote = sb.d_cons;  // where the codes of this sub-pass's rows are, once somebody has voted
         if (sb.chg.cap) {
             // change points of the batch: flags for the reads this sub-pass has just finished, behind the last kernel that writes their
             // rows (or codes); the scan and the gather behind the batch's last sub-pass.  Row ra - 1 of a batch cut into passes was
@@ -2697,6 +2740,72 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
                 skx::launch_change_events(ls, L.d_chg_flag, L.d_chg_pos, L.d_chg_bsum, sb.chg.n_batch, sb.chg.cap, sb.chg.n_events,
                                           sb.chg.ev_read, sb.chg.ev_idx ? d_topk_idx : nullptr, sb.chg.ev_sum ? d_topk_sum : nullptr, w_idx,
                                           sb.chg.ev_idx, sb.chg.ev_sum, sb.chg.ev_codes ? d_codes : nullptr, w_codes, sb.chg.ev_codes);
+            if (d_codes) d_vote = d_codes;
+        }
+        if (sb.call.any()) {
+            // species call of the batch: the selection over the reads this sub-pass has just finished, behind the last kernel that writes
+            // their rows (or codes), with its flags; the scan and the gathers behind the batch's last sub-pass -- as the change points above
+            const CallOut& co = sb.call;
+            if (co.cap && sb.ra != 0 && li != 0) return fail(SKX_ERR_HIP, "internal: a later pass of a batch left lane 0");
+            const u32 nf = ref->n_features, key_w = 1u + std::max(st->top_k, nf);
+            const size_t mr = st->max_reads;
+            u32* d_codes = nullptr;
+            if (co.wants_codes()) {
+                d_codes = d_vote;
+                if (!d_codes) {  // (no consensus output travels with the batch: the vote goes to the lane's own scratch)
+                    if (!L.d_chg_codes) HIPCHK(hipMalloc(&L.d_chg_codes, mr * n_sp * nf * 4));
+                    d_codes = L.d_chg_codes;
+                    skx::launch_consensus_rows(ls, d_topk_idx, out_r0, n_reads, n_sp, st->top_k, ref->d_sp_g0, ref->d_codes, nf, d_codes, n_pad);
+                }
+            }
+            // where the compact rows go: the bound arrays, or -- an event list needs rows the call leaves out -- the lane's scratch
+            u32 *c_sp = co.sp, *c_idx = co.idx, *c_codes = co.codes, *c_key = nullptr;
+            u64* c_sum = co.sum;
+            if (!c_sp) {
+                if (!L.d_call_sp) HIPCHK(hipMalloc(&L.d_call_sp, mr * 4));
+                c_sp = L.d_call_sp;
+            }
+            if (co.cap) {
+                if (!L.d_call_flag) {
+                    HIPCHK(hipMalloc(&L.d_call_flag, mr * 4));
+                    HIPCHK(hipMalloc(&L.d_call_pos, mr * 4));
+                    HIPCHK(hipMalloc(&L.d_call_bsum, (mr / 1024 + 1) * 4));
+                }
+                // (the reference may get its genotype table after this lane's first event list: the key of a codes-mode list is then wider
+                // than the room sized before.  A batch's passes all have one width, so the key never grows inside a batch; hipFree waits
+                // for whatever the lane still has queued)
+                if (L.call_key_w < key_w) {
+                    (void)hipFree(L.d_call_key);
+                    L.d_call_key = nullptr; L.call_key_w = 0;
+                    HIPCHK(hipMalloc(&L.d_call_key, mr * key_w * 4));
+                    L.call_key_w = key_w;
+                }
+                c_key = L.d_call_key;
+                if (co.ev_idx && !c_idx) {
+                    if (!L.d_call_idx) HIPCHK(hipMalloc(&L.d_call_idx, mr * st->top_k * 4));
+                    c_idx = L.d_call_idx;
+                }
+                if (co.ev_sum && !c_sum) {
+                    if (!L.d_call_sum) HIPCHK(hipMalloc(&L.d_call_sum, mr * st->top_k * 8));
+                    c_sum = L.d_call_sum;
+                }
+                if (co.ev_codes && !c_codes) {
+                    if (!L.d_call_codes) HIPCHK(hipMalloc(&L.d_call_codes, mr * nf * 4));
+                    c_codes = L.d_call_codes;
+                }
+            }
+            const bool key_codes = co.ev_codes != nullptr;
+            skx::launch_species_call(ls, d_topk_idx, d_topk_sum, d_codes, sb.ra, sb.rb, n_sp, st->top_k, nf, c_sp, c_idx, c_sum, c_codes, c_key,
+                                     key_codes);
+            if (co.cap) {
+                skx::launch_change_flags(ls, c_key, 1u + (key_codes ? nf : st->top_k), sb.ra, sb.rb, L.d_call_flag);
+                if (sb.rb == co.n_batch) {
+                    skx::launch_change_events(ls, L.d_call_flag, L.d_call_pos, L.d_call_bsum, co.n_batch, co.cap, co.n_events, co.ev_read,
+                                              co.ev_idx ? c_idx : nullptr, co.ev_sum ? c_sum : nullptr, st->top_k, co.ev_idx, co.ev_sum,
+                                              co.ev_codes ? c_codes : nullptr, nf, co.ev_codes);
+                    if (co.ev_sp) skx::launch_call_species_gather(ls, L.d_call_flag, L.d_call_pos, co.n_batch, co.cap, c_sp, co.ev_sp);
+                }
+            }
         }
     }
     if (sb.d_shared)
@@ -2736,10 +2845,11 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
 static int run_pass(skx_stream* st, u32 ra, u32 rb, u32 p_base, u32 P, u32* d_topk_idx, u64* d_topk_sum,
                     u32* d_shared /* [rb-ra][n_genomes] or NULL */, bool update_table, bool inserted = false, u32 q_rows = 0xFFFFFFFFu,
                     void* slot = nullptr, u32* d_counts = nullptr /* [rb-ra][n_pad] or NULL */, u32* d_cons = nullptr,
-                    const ChangeOut* chg = nullptr) {
+                    const ChangeOut* chg = nullptr, const CallOut* call = nullptr) {
     SubPass sb;
     sb.slot = slot; sb.d_cons = d_cons;
     if (chg) sb.chg = *chg;
+    if (call) sb.call = *call;
     sb.ra = ra; sb.rb = rb; sb.p_off = 0; sb.P = P; sb.p_base = p_base; sb.d_topk_idx = d_topk_idx; sb.d_topk_sum = d_topk_sum;
     sb.d_shared = d_shared; sb.d_counts = d_counts; sb.side = st->side;
     sb.d_poff = st->d_poff_pass[st->pslot];  // (inserted passes: the front half's copy; else run_pass_multi fills the slot itself)
@@ -3136,7 +3246,7 @@ static int batch_back(skx_stream* st, PendingBatch& pb, PendingBatch* younger) {
             HIPCHK(hipMalloc(&d_shared, (size_t)(rb - ra) * ref->n_genomes * 4));
         }
         SKXCHK(run_pass(st, ra, rb, p_base, P, pb.d_topk_idx, pb.d_topk_sum, d_shared, true, inserted, inserted ? q_rows : 0xFFFFFFFFu,
-                        rb == n_reads ? pb.slot : nullptr, nullptr, pb.d_cons, &pb.chg));
+                        rb == n_reads ? pb.slot : nullptr, nullptr, pb.d_cons, &pb.chg, &pb.call));
         inserted = false;
         st->last_passes += 1;
         if (pb.h_shared) {
@@ -3243,7 +3353,7 @@ static int batch_back_group(skx_stream* st, PendingBatch* g, int n, PendingBatch
         subs[i].d_topk_idx = g[i].d_topk_idx; subs[i].d_topk_sum = g[i].d_topk_sum;
         subs[i].p_off = p_off; subs[i].P = P[i];
         subs[i].d_poff = st->d_poff_pass[g[0].spec_slot] + (size_t)i * ((size_t)st->rpass + 2);
-        subs[i].slot = g[i].slot; subs[i].d_cons = g[i].d_cons; subs[i].chg = g[i].chg;
+        subs[i].slot = g[i].slot; subs[i].d_cons = g[i].d_cons; subs[i].chg = g[i].chg; subs[i].call = g[i].call;
         p_off += P[i];
     }
     st->last_pairs = pairs; st->last_passes = 1; st->shared_passes += 1;
@@ -3289,7 +3399,7 @@ static int flush_pending(skx_stream* st) {
 // h_shared / h_sketches / h_sketch_len: optional HOST outputs (parity/debug).
 static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_offsets, u32 n_reads, u64 n_bases, u32* d_topk_idx,
                          u64* d_topk_sum, u32* h_shared, u64* h_sketches, u32* h_sketch_len, u32* d_cons = nullptr,
-                         const ChangeOut* chg = nullptr) {
+                         const ChangeOut* chg = nullptr, const CallOut* call = nullptr) {
     if (n_reads == 0) return SKX_OK;
     SKXCHK(flush_pending(st));
     PendingBatch pb;
@@ -3297,6 +3407,7 @@ static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_of
     pb.d_topk_idx = d_topk_idx; pb.d_topk_sum = d_topk_sum;
     pb.h_shared = h_shared; pb.h_sketches = h_sketches; pb.h_sketch_len = h_sketch_len; pb.d_cons = d_cons;
     if (chg) { pb.chg = *chg; pb.chg.n_batch = n_reads; }
+    if (call) { pb.call = *call; pb.call.n_batch = n_reads; }
     SKXCHK(batch_front(st, pb));
     st->tail_pass = true;  // (a synchronous push: the batch's passes have the chip to themselves)
     const int rc = batch_back(st, pb, nullptr);
@@ -3308,10 +3419,11 @@ static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_of
 // next group runs the shared back half of the one before it, behind its own front half.  Errors of a batch surface here up to
 // stream_coalesce calls late (or in the flush); the batches enqueued after it up to that call are dropped too.
 static int enqueue_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_offsets, u32 n_reads, u64 n_bases, u32* d_topk_idx,
-                         u64* d_topk_sum, void* slot, u32* d_cons, const ChangeOut* chg = nullptr) {
+                         u64* d_topk_sum, void* slot, u32* d_cons, const ChangeOut* chg = nullptr, const CallOut* call = nullptr) {
     PendingBatch nw;
     nw.d_cons = d_cons;
     if (chg) { nw.chg = *chg; nw.chg.n_batch = n_reads; }
+    if (call) { nw.call = *call; nw.call.n_batch = n_reads; }
     nw.d_bases = d_bases; nw.d_offsets = d_offsets; nw.n_reads = n_reads; nw.n_bases = n_bases;
     nw.d_topk_idx = d_topk_idx; nw.d_topk_sum = d_topk_sum; nw.slot = slot;
     nw.pairable = st->coalesce >= 2;
@@ -3432,17 +3544,118 @@ SKX_API int skx_stream_bind_changes(skx_stream* st, uint32_t cap, uint32_t* n_ev
     return SKX_OK;
 }
 
+// ---- species call of a batch (skx_stream_bind_call, skx_stream_bind_call_changes): two one-shot bindings kept in one CallOut, taken
+// together by every batch entry point first
+static CallOut take_call(skx_stream* st) {
+    const CallOut c = st->bound_call;
+    st->bound_call = CallOut{};
+    return c;
+}
+static int check_call(const char* who, const skx_stream* st, const CallOut& c, bool device_entry, const void* device_idx, const void* device_sum) {
+    if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: a species call is bound but the stream was created with top_k=0", who);
+    if (c.wants_codes() && !st->ref->d_codes)
+        return fail(SKX_ERR_INVALID, "%s: a species call with codes is bound but the reference has no genotype table", who);
+    if (device_entry && (!device_idx || !device_sum))
+        return fail(SKX_ERR_INVALID, "%s: a species call is bound but d_topk_idx or d_topk_sum is NULL", who);
+    return SKX_OK;
+}
+// device arrays of a call for host-fed batches (push: the stream's, submit: a slot's): compact rows for max_reads reads, each allocated
+// when first asked for; event arrays for `cap` entries, which grow like ensure_events' (the caller has made sure nothing queued uses them)
+static int ensure_call(const skx_stream* st, CallOut& d, const CallOut& want) {
+    const size_t mr = st->max_reads, top = st->top_k, nf = st->ref->n_features;
+    if (want.on) {
+        if (!d.sp) HIPCHK(hipMalloc(&d.sp, mr * 4));
+        if (want.idx && !d.idx) HIPCHK(hipMalloc(&d.idx, mr * top * 4));
+        if (want.sum && !d.sum) HIPCHK(hipMalloc(&d.sum, mr * top * 8));
+        if (want.codes && !d.codes) HIPCHK(hipMalloc(&d.codes, mr * nf * 4));
+    }
+    const u32 cap = std::min<u32>(want.cap, st->max_reads);
+    if (cap == 0 || (d.n_events && d.cap >= cap && (!want.ev_codes || d.ev_codes))) return SKX_OK;
+    (void)hipFree(d.n_events); (void)hipFree(d.ev_read); (void)hipFree(d.ev_sp); (void)hipFree(d.ev_idx); (void)hipFree(d.ev_sum); (void)hipFree(d.ev_codes);
+    d.n_events = d.ev_read = d.ev_sp = d.ev_idx = d.ev_codes = nullptr; d.ev_sum = nullptr;
+    const size_t keep = std::max(cap, d.cap);
+    d.cap = 0;
+    HIPCHK(hipMalloc(&d.n_events, 4));
+    HIPCHK(hipMalloc(&d.ev_read, keep * 4));
+    HIPCHK(hipMalloc(&d.ev_sp, keep * 4));
+    HIPCHK(hipMalloc(&d.ev_idx, keep * top * 4));
+    HIPCHK(hipMalloc(&d.ev_sum, keep * top * 8));
+    if (nf) HIPCHK(hipMalloc(&d.ev_codes, keep * nf * 4));
+    d.cap = (u32)keep;
+    return SKX_OK;
+}
+// what the kernels get: the device arrays `d` for the outputs the caller asked for in `want`
+static CallOut device_call(const CallOut& want, const CallOut& d) {
+    CallOut c;
+    c.on = want.on;
+    if (want.on) {
+        c.sp = d.sp;
+        c.idx = want.idx ? d.idx : nullptr;
+        c.sum = want.sum ? d.sum : nullptr;
+        c.codes = want.codes ? d.codes : nullptr;
+    }
+    if (want.cap) {
+        c.cap = std::min(want.cap, d.cap);
+        c.n_events = d.n_events; c.ev_read = d.ev_read; c.ev_sp = d.ev_sp;
+        c.ev_idx = want.ev_idx ? d.ev_idx : nullptr;
+        c.ev_sum = want.ev_sum ? d.ev_sum : nullptr;
+        c.ev_codes = want.ev_codes ? d.ev_codes : nullptr;
+    }
+    return c;
+}
+// the compact rows of n_reads reads from the device arrays `d` to the caller's, queued on hs (page-locked or pageable host memory)
+static int copy_call_rows(const skx_stream* st, const CallOut& want, const CallOut& d, u32 n_reads, hipStream_t hs) {
+    if (!want.on) return SKX_OK;
+    const size_t n = n_reads, top = st->top_k, nf = st->ref->n_features;
+    HIPCHK(hipMemcpyAsync(want.sp, d.sp, n * 4, hipMemcpyDeviceToHost, hs));
+    if (want.idx) HIPCHK(hipMemcpyAsync(want.idx, d.idx, n * top * 4, hipMemcpyDeviceToHost, hs));
+    if (want.sum) HIPCHK(hipMemcpyAsync(want.sum, d.sum, n * top * 8, hipMemcpyDeviceToHost, hs));
+    if (want.codes) HIPCHK(hipMemcpyAsync(want.codes, d.codes, n * nf * 4, hipMemcpyDeviceToHost, hs));
+    return SKX_OK;
+}
+// the first min(n, cap) events of the device arrays `d` to the caller's host arrays; nothing past them is touched
+static int deliver_call_events(const skx_stream* st, const CallOut& want, const CallOut& d, u32 n) {
+    *want.n_events = n;
+    const size_t m = std::min(n, std::min(want.cap, d.cap)), top = st->top_k, nf = st->ref->n_features;
+    if (m == 0) return SKX_OK;
+    HIPCHK(hipMemcpy(want.ev_read, d.ev_read, m * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(want.ev_sp, d.ev_sp, m * 4, hipMemcpyDeviceToHost));
+    if (want.ev_idx) HIPCHK(hipMemcpy(want.ev_idx, d.ev_idx, m * top * 4, hipMemcpyDeviceToHost));
+    if (want.ev_sum) HIPCHK(hipMemcpy(want.ev_sum, d.ev_sum, m * top * 8, hipMemcpyDeviceToHost));
+    if (want.ev_codes) HIPCHK(hipMemcpy(want.ev_codes, d.ev_codes, m * nf * 4, hipMemcpyDeviceToHost));
+    return SKX_OK;
+}
+
+SKX_API int skx_stream_bind_call(skx_stream* st, uint32_t* call_species, uint32_t* call_idx, uint64_t* call_sum, uint32_t* call_codes) {
+    if (!st || !call_species) return fail(SKX_ERR_INVALID, "skx_stream_bind_call: NULL argument");
+    CallOut& c = st->bound_call;
+    c.on = true; c.sp = call_species; c.idx = call_idx; c.sum = reinterpret_cast<u64*>(call_sum); c.codes = call_codes;
+    return SKX_OK;
+}
+SKX_API int skx_stream_bind_call_changes(skx_stream* st, uint32_t cap, uint32_t* n_events, uint32_t* ev_read, uint32_t* ev_species,
+                                         uint32_t* ev_idx, uint64_t* ev_sum, uint32_t* ev_codes) {
+    if (!st || !n_events || !ev_read || !ev_species) return fail(SKX_ERR_INVALID, "skx_stream_bind_call_changes: NULL argument");
+    if (cap == 0) return fail(SKX_ERR_INVALID, "skx_stream_bind_call_changes: cap must be at least 1");
+    CallOut& c = st->bound_call;
+    c.cap = cap; c.n_events = n_events; c.ev_read = ev_read; c.ev_sp = ev_species; c.ev_idx = ev_idx;
+    c.ev_sum = reinterpret_cast<u64*>(ev_sum); c.ev_codes = ev_codes;
+    return SKX_OK;
+}
+
 SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads,
                             uint32_t* topk_idx, uint64_t* topk_sum, uint32_t* per_read_shared, uint64_t* sketches,
                             uint32_t* sketch_len) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL argument");
     u32* const cons = take_consensus(st);
     const ChangeOut chg = take_changes(st);
+    const CallOut call = take_call(st);
     if (!offsets) return fail(SKX_ERR_INVALID, "NULL argument");
     if (cons) SKXCHK(check_consensus("skx_stream_push", st, false, nullptr));
     if (chg.cap) SKXCHK(check_changes("skx_stream_push", st, chg, false, nullptr));
+    if (call.any()) SKXCHK(check_call("skx_stream_push", st, call, false, nullptr, nullptr));
     if (n_reads == 0) {
         if (chg.cap) *chg.n_events = 0;
+        if (call.cap) *call.n_events = 0;
         return SKX_OK;
     }
     if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
@@ -3454,13 +3667,18 @@ SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t
     if (n_bases && !bases) return fail(SKX_ERR_INVALID, "bases is NULL");
     if ((topk_idx || topk_sum) && st->top_k == 0) return fail(SKX_ERR_INVALID, "stream was created with top_k=0");
     SKXCHK(use_device(st->device));
-    const bool vote = cons || chg.codes;  // (an event list of codes votes into the same scratch)
+    const bool vote = cons || chg.codes || call.wants_codes();  // (an event list of codes and a call with codes vote into the same scratch)
     if (vote && !st->d_cons) HIPCHK(hipMalloc(&st->d_cons, consensus_bytes(st, st->max_reads)));
     SKXCHK(flush_pending(st));
     ChangeOut d_chg;
     if (chg.cap) {  // (pushes are synchronous: nothing queued uses the stream's event arrays)
         SKXCHK(ensure_events(st, st->d_ev, std::min(chg.cap, st->max_reads), chg.codes));
         d_chg = device_events(chg, st->d_ev);
+    }
+    CallOut d_call;
+    if (call.any()) {
+        SKXCHK(ensure_call(st, st->d_call, call));
+        d_call = device_call(call, st->d_call);
     }
     hipStream_t hs = st->hs0;
     // rebase offsets to 0 on the way in (packed input: to the first byte that holds a base of the batch)
@@ -3470,7 +3688,8 @@ SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t
     HIPCHK(hipMemcpyAsync(st->d_offsets, st->h_offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, hs));
     if (n_bases) HIPCHK(hipMemcpyAsync(st->d_bases, bases + byte0, n_bytes, hipMemcpyHostToDevice, hs));
     SKXCHK(process_batch(st, st->d_bases, st->d_offsets, n_reads, n_bases, st->d_topk_idx, st->d_topk_sum,
-                         per_read_shared, reinterpret_cast<u64*>(sketches), sketch_len, vote ? st->d_cons : nullptr, chg.cap ? &d_chg : nullptr));
+                         per_read_shared, reinterpret_cast<u64*>(sketches), sketch_len, vote ? st->d_cons : nullptr, chg.cap ? &d_chg : nullptr,
+                         call.any() ? &d_call : nullptr));
     SKXCHK(queue_chains(st, true));    // the ranking of the batch's last pass (waits for its candidates)
     HIPCHK(hipStreamSynchronize(hs));  // sketch copies (first stream)
     const size_t rows = (size_t)n_reads * st->ref->n_species * st->top_k;
@@ -3479,8 +3698,12 @@ SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t
     if (cons) HIPCHK(hipMemcpyAsync(cons, st->d_cons, consensus_bytes(st, n_reads), hipMemcpyDeviceToHost, st->hs2));
     u32 n_ev = 0;
     if (chg.cap) HIPCHK(hipMemcpyAsync(&n_ev, st->d_ev.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
+    u32 n_cev = 0;
+    SKXCHK(copy_call_rows(st, call, st->d_call, n_reads, st->hs2));
+    if (call.cap) HIPCHK(hipMemcpyAsync(&n_cev, st->d_call.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
     HIPCHK(hipStreamSynchronize(st->hs2));  // the rows are written by the back half
     if (chg.cap) SKXCHK(deliver_events(st, chg, st->d_ev, n_ev));
+    if (call.cap) SKXCHK(deliver_call_events(st, call, st->d_call, n_cev));
     if (st->profiling) collect_spans(st);
     return SKX_OK;
 }
@@ -3499,38 +3722,43 @@ SKX_API int skx_stream_push_device(skx_stream* st, const uint8_t* d_bases, const
                                    uint64_t n_bases, uint32_t* d_topk_idx, uint64_t* d_topk_sum) {
     u32* const cons = st ? take_consensus(st) : nullptr;
     const ChangeOut chg = st ? take_changes(st) : ChangeOut{};
+    const CallOut call = st ? take_call(st) : CallOut{};
     SKXCHK(check_device_batch(st, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum));
     if (cons) SKXCHK(check_consensus("skx_stream_push_device", st, true, d_topk_idx));
     if (chg.cap) SKXCHK(check_changes("skx_stream_push_device", st, chg, true, d_topk_idx));
+    if (call.any()) SKXCHK(check_call("skx_stream_push_device", st, call, true, d_topk_idx, d_topk_sum));
     SKXCHK(use_device(st->device));
     if (n_reads == 0) {
         SKXCHK(flush_pending(st));
         if (chg.cap) HIPCHK(hipMemsetAsync(chg.n_events, 0, 4, st->hs2));
+        if (call.cap) HIPCHK(hipMemsetAsync(call.n_events, 0, 4, st->hs2));
         return SKX_OK;
     }
     u32* ti = d_topk_idx ? d_topk_idx : st->d_topk_idx;
     u64* ts = d_topk_sum ? reinterpret_cast<u64*>(d_topk_sum) : st->d_topk_sum;
     return process_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, nullptr, nullptr, cons,
-                         chg.cap ? &chg : nullptr);
+                         chg.cap ? &chg : nullptr, call.any() ? &call : nullptr);
 }
 SKX_API int skx_stream_enqueue_device(skx_stream* st, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
                                       uint64_t n_bases, uint32_t* d_topk_idx, uint64_t* d_topk_sum) {
     u32* const cons = st ? take_consensus(st) : nullptr;
     const ChangeOut chg = st ? take_changes(st) : ChangeOut{};
+    const CallOut call = st ? take_call(st) : CallOut{};
     SKXCHK(check_device_batch(st, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum));
     if (cons) SKXCHK(check_consensus("skx_stream_enqueue_device", st, true, d_topk_idx));
     if (chg.cap) SKXCHK(check_changes("skx_stream_enqueue_device", st, chg, true, d_topk_idx));
+    if (call.any()) SKXCHK(check_call("skx_stream_enqueue_device", st, call, true, d_topk_idx, d_topk_sum));
     if (n_reads == 0) {
-        if (chg.cap) {
-            SKXCHK(use_device(st->device));
-            HIPCHK(hipMemsetAsync(chg.n_events, 0, 4, st->hs2));
-        }
+        if (chg.cap || call.cap) SKXCHK(use_device(st->device));
+        if (chg.cap) HIPCHK(hipMemsetAsync(chg.n_events, 0, 4, st->hs2));
+        if (call.cap) HIPCHK(hipMemsetAsync(call.n_events, 0, 4, st->hs2));
         return SKX_OK;
     }
     SKXCHK(use_device(st->device));
     u32* ti = d_topk_idx ? d_topk_idx : st->d_topk_idx;
     u64* ts = d_topk_sum ? reinterpret_cast<u64*>(d_topk_sum) : st->d_topk_sum;
-    return enqueue_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, cons, chg.cap ? &chg : nullptr);
+    return enqueue_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, cons, chg.cap ? &chg : nullptr,
+                         call.any() ? &call : nullptr);
 }
 SKX_API int skx_stream_flush(skx_stream* st) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
@@ -3548,6 +3776,8 @@ static int staged_rows(skx_stream* st, void* slot) {
     if (sl.out_sum) HIPCHK(hipMemcpyAsync(sl.out_sum, sl.d_rows_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
     if (sl.out_cons) HIPCHK(hipMemcpyAsync(sl.out_cons, sl.d_cons, consensus_bytes(st, sl.n_reads), hipMemcpyDeviceToHost, st->hs2));
     if (sl.out_chg.cap) HIPCHK(hipMemcpyAsync(sl.h_ev_n, sl.d_ev.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
+    SKXCHK(copy_call_rows(st, sl.out_call, sl.d_call, sl.n_reads, st->hs2));
+    if (sl.out_call.cap) HIPCHK(hipMemcpyAsync(sl.h_cev_n, sl.d_call.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
     HIPCHK(hipEventRecord(sl.ev_done, st->hs2));
     sl.in_flight = true;
     return SKX_OK;
@@ -3556,10 +3786,13 @@ static int staged_rows(skx_stream* st, void* slot) {
 // known only now, and nothing past min(n_events, cap) may be written
 static int staged_landed(skx_stream* st, skx_stream::Staged& sl) {
     sl.in_flight = false;
-    if (!sl.out_chg.cap) return SKX_OK;
     const ChangeOut want = sl.out_chg;
+    const CallOut want_call = sl.out_call;
     sl.out_chg = ChangeOut{};
-    return deliver_events(st, want, sl.d_ev, *static_cast<volatile u32*>(sl.h_ev_n));
+    sl.out_call = CallOut{};
+    if (want.cap) SKXCHK(deliver_events(st, want, sl.d_ev, *static_cast<volatile u32*>(sl.h_ev_n)));
+    if (want_call.cap) SKXCHK(deliver_call_events(st, want_call, sl.d_call, *static_cast<volatile u32*>(sl.h_cev_n)));
+    return SKX_OK;
 }
 static void staged_drop(void* slot) {
     if (slot) static_cast<skx_stream::Staged*>(slot)->dropped = true;
@@ -3571,8 +3804,11 @@ static int staged_process(skx_stream* st, skx_stream::Staged& sl) {
     HIPCHK(hipStreamWaitEvent(st->hs0, sl.ev_copy, 0));  // the batch must have landed before the sketcher reads it
     ChangeOut d_chg;
     if (sl.out_chg.cap) d_chg = device_events(sl.out_chg, sl.d_ev);
+    CallOut d_call;
+    if (sl.out_call.any()) d_call = device_call(sl.out_call, sl.d_call);
     return enqueue_batch(st, sl.d_bases, sl.d_offsets, sl.n_reads, sl.n_bases, sl.d_rows_idx, sl.d_rows_sum, &sl,
-                         (sl.out_cons || sl.out_chg.codes) ? sl.d_cons : nullptr, sl.out_chg.cap ? &d_chg : nullptr);
+                         (sl.out_cons || sl.out_chg.codes || sl.out_call.wants_codes()) ? sl.d_cons : nullptr, sl.out_chg.cap ? &d_chg : nullptr,
+                         sl.out_call.any() ? &d_call : nullptr);
 }
 // ... until its rows are on the host
 static int staged_finish(skx_stream* st, skx_stream::Staged& sl) {
@@ -3593,9 +3829,11 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
     if (!st) return fail(SKX_ERR_INVALID, "NULL argument");
     u32* const cons = take_consensus(st);
     const ChangeOut chg = take_changes(st);
+    const CallOut call = take_call(st);
     if (!offsets) return fail(SKX_ERR_INVALID, "NULL argument");
     if (cons) SKXCHK(check_consensus("skx_stream_submit", st, false, nullptr));
     if (chg.cap) SKXCHK(check_changes("skx_stream_submit", st, chg, false, nullptr));
+    if (call.any()) SKXCHK(check_call("skx_stream_submit", st, call, false, nullptr, nullptr));
     if (n_reads == 0) return fail(SKX_ERR_INVALID, "empty batch");
     if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
     for (u32 r = 0; r < n_reads; ++r)
@@ -3639,6 +3877,11 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
         if (!sl.h_ev_n) HIPCHK(hipHostMalloc((void**)&sl.h_ev_n, 4, hipHostMallocDefault));
         if (chg.codes && !sl.d_cons) HIPCHK(hipMalloc(&sl.d_cons, consensus_bytes(st, st->max_reads)));
     }
+    if (call.any()) {  // (likewise: the slot's compact rows and its call events)
+        SKXCHK(ensure_call(st, sl.d_call, call));
+        if (call.cap && !sl.h_cev_n) HIPCHK(hipHostMalloc((void**)&sl.h_cev_n, 4, hipHostMallocDefault));
+        if (call.wants_codes() && !sl.d_cons) HIPCHK(hipMalloc(&sl.d_cons, consensus_bytes(st, st->max_reads)));
+    }
     const u64 byte0 = st->packed ? base0 >> 1 : base0, rebase = st->packed ? byte0 * 2 : base0;
     const u64 n_bytes = st->packed ? ((offsets[n_reads] + 1) >> 1) - byte0 : n_bases;
     for (u32 r = 0; r <= n_reads; ++r) sl.h_offsets[r] = offsets[r] - rebase;
@@ -3648,6 +3891,7 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
     sl.pending = true; sl.dropped = false; sl.n_reads = n_reads; sl.n_bases = n_bases; sl.out_idx = topk_idx; sl.out_sum = reinterpret_cast<u64*>(topk_sum);
     sl.out_cons = cons;
     sl.out_chg = chg;
+    sl.out_call = call;
     sl.ticket = st->next_ticket;
     if (ticket) *ticket = st->next_ticket;
     st->next_ticket += 1;
@@ -4603,6 +4847,50 @@ SKX_API int skx_changes_rows(int device, const uint32_t* rows, uint64_t n_rows, 
         total += n_ev - first;
     }
     *n_events = total;
+    return SKX_OK;
+}
+
+// Species call of rows that live on the host: chunks of at most kCallRowsBytes of input rows through species_call_kernel.  Rows are
+// independent, so chunks need no seam.
+static const u64 kCallRowsBytes = 64ull << 20;
+SKX_API int skx_call_rows(int device, const uint32_t* idx, const uint64_t* sum, const uint32_t* codes, uint64_t n_rows, uint32_t n_species,
+                          uint32_t top_k, uint32_t n_features, uint32_t* call_species, uint32_t* call_idx, uint64_t* call_sum,
+                          uint32_t* call_codes) {
+    if (!idx || !sum || !call_species) return fail(SKX_ERR_INVALID, "skx_call_rows: NULL argument");
+    if (n_species < 1 || n_species > SKX_MAX_SPECIES) return fail(SKX_ERR_INVALID, "skx_call_rows: n_species = %u outside 1..%u", n_species, SKX_MAX_SPECIES);
+    if (top_k < 1 || top_k > SKX_MAX_TOP) return fail(SKX_ERR_INVALID, "skx_call_rows: top_k = %u outside 1..%u", top_k, SKX_MAX_TOP);
+    if ((codes != nullptr) != (call_codes != nullptr)) return fail(SKX_ERR_INVALID, "skx_call_rows: codes and call_codes go together");
+    if (codes && (n_features < 1 || n_features > SKX_MAX_FEATURES))
+        return fail(SKX_ERR_INVALID, "skx_call_rows: n_features = %u outside 1..%u", n_features, SKX_MAX_FEATURES);
+    if (n_rows == 0) return SKX_OK;
+    SKXCHK(use_device(device));
+    const size_t w_in = (size_t)n_species * top_k, w_cin = codes ? (size_t)n_species * n_features : 0;
+    u64 chunk = std::min<u64>(n_rows, std::max<u64>(1, kCallRowsBytes / (w_in * 12 + w_cin * 4)));
+#ifdef SKX_EXPERIMENTS
+    if (const char* e = skx::knob("SKX_CALL_ROWS")) chunk = std::min<u64>(n_rows, std::max<u64>(1, strtoull(e, nullptr, 10)));  // (tests: chunks at toy size)
+#endif
+    DevMem m_idx, m_sum, m_codes, m_sp, m_cidx, m_csum, m_ccodes;
+    HIPCHK(m_idx.need(chunk * w_in * 4));
+    HIPCHK(m_sum.need(chunk * w_in * 8));
+    if (codes) HIPCHK(m_codes.need(chunk * w_cin * 4));
+    HIPCHK(m_sp.need(chunk * 4));
+    if (call_idx) HIPCHK(m_cidx.need(chunk * top_k * 4));
+    if (call_sum) HIPCHK(m_csum.need(chunk * top_k * 8));
+    if (call_codes) HIPCHK(m_ccodes.need(chunk * n_features * 4));
+    for (u64 r0 = 0; r0 < n_rows; r0 += chunk) {
+        const u32 n = (u32)std::min(chunk, n_rows - r0);
+        HIPCHK(hipMemcpy(m_idx.p, idx + r0 * w_in, (size_t)n * w_in * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(m_sum.p, sum + r0 * w_in, (size_t)n * w_in * 8, hipMemcpyHostToDevice));
+        if (codes) HIPCHK(hipMemcpy(m_codes.p, codes + r0 * w_cin, (size_t)n * w_cin * 4, hipMemcpyHostToDevice));
+        skx::launch_species_call(nullptr, m_idx.as<u32>(), m_sum.as<u64>(), codes ? m_codes.as<u32>() : nullptr, 0, n, n_species, top_k,
+                                 n_features, m_sp.as<u32>(), call_idx ? m_cidx.as<u32>() : nullptr, call_sum ? m_csum.as<u64>() : nullptr,
+                                 call_codes ? m_ccodes.as<u32>() : nullptr, nullptr, false);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpy(call_species + r0, m_sp.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (call_idx) HIPCHK(hipMemcpy(call_idx + r0 * top_k, m_cidx.p, (size_t)n * top_k * 4, hipMemcpyDeviceToHost));
+        if (call_sum) HIPCHK(hipMemcpy(call_sum + r0 * top_k, m_csum.p, (size_t)n * top_k * 8, hipMemcpyDeviceToHost));
+        if (call_codes) HIPCHK(hipMemcpy(call_codes + r0 * n_features, m_ccodes.p, (size_t)n * n_features * 4, hipMemcpyDeviceToHost));
+    }
     return SKX_OK;
 }
 

@@ -18,6 +18,8 @@
 //                          running table and per-read (sum desc, index asc) top-k, pruned      (A1, A7)
 //   consensus_rows / change_flags / change_gather
 //                          behind a batch's rows: consensus codes; the reads whose call differs from the read before
+//   species_call / call_species_gather
+//                          behind a multi-species batch's rows: the species with the largest leader and its rows, compact
 //
 // Integer work throughout (u64 hash compares, bit counts): no MFMA.
 #include <algorithm>
@@ -5361,6 +5363,66 @@ __global__ __launch_bounds__(256) void change_gather_kernel(const u32* __restric
     }
 }
 
+// ---- species call of finished rows (skx_stream_bind_call, skx_stream_bind_call_changes, skx_call_rows): per read the species whose
+// leader has the largest running sum -- the lowest such species -- and that species' rows alone, compact.
+// A wave takes 64 adjacent reads.  (1) a lane per read walks the n_sp leads sum[r][sp][0] (one u64 each; strictly greater replaces, so the
+// lowest species wins ties and all-zero leads call species 0).  (2) the wave's compact outputs are one contiguous stretch per array --
+// 64 x top_k indices, 64 x top_k sums, 64 x n_feat codes, 64 x key_w key words -- and the lanes run ALONG that stretch: element e belongs
+// to read e / width, whose species comes from its lane by a shuffle; stores are contiguous across the wave, loads contiguous within a
+// row.  The loops are wave-uniform (width steps), only loads and stores are predicated.  Every output element has one writer; launches
+// over disjoint [ra, rb) share nothing.  key row = {species, index row | codes}: what launch_change_flags compares.
+__global__ __launch_bounds__(256) void species_call_kernel(const u32* __restrict__ idx, const u64* __restrict__ sum,
+                                                           const u32* __restrict__ codes, u32 ra, u32 rb, u32 n_sp, u32 top_k, u32 n_feat,
+                                                           u32* __restrict__ call_sp, u32* __restrict__ call_idx, u64* __restrict__ call_sum,
+                                                           u32* __restrict__ call_codes, u32* __restrict__ key, u32 key_codes) {
+    const u32 lane = lane_id();
+    const u64 r0 = (u64)ra + ((u64)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u;
+    if (r0 >= rb) return;  // (wave-uniform)
+    const u32 n_here = (u64)rb - r0 < 64u ? (u32)((u64)rb - r0) : 64u;
+    u32 c = 0;
+    if (lane < n_here) {
+        const u64* lead = sum + (r0 + lane) * n_sp * top_k;
+        u64 best = lead[0];
+        for (u32 sp = 1; sp < n_sp; ++sp) {
+            const u64 v = lead[(size_t)sp * top_k];
+            if (v > best) { best = v; c = sp; }
+        }
+        call_sp[r0 + lane] = c;
+    }
+    if (call_idx || call_sum)
+        for (u32 i = 0; i < top_k; ++i) {
+            const u32 e = i * 64u + lane, rr = e / top_k, j = e - rr * top_k;
+            const u32 sp = (u32)__shfl((int)c, (int)rr, 64);
+            if (rr < n_here) {
+                const size_t src = ((r0 + rr) * n_sp + sp) * top_k + j, dst = r0 * top_k + e;
+                if (call_idx) call_idx[dst] = idx[src];
+                if (call_sum) call_sum[dst] = sum[src];
+            }
+        }
+    if (call_codes)
+        for (u32 i = 0; i < n_feat; ++i) {
+            const u32 e = i * 64u + lane, rr = e / n_feat, j = e - rr * n_feat;
+            const u32 sp = (u32)__shfl((int)c, (int)rr, 64);
+            if (rr < n_here) call_codes[r0 * n_feat + e] = codes[((r0 + rr) * n_sp + sp) * n_feat + j];
+        }
+    if (key) {
+        const u32 w = key_codes ? n_feat : top_k, key_w = 1u + w;
+        const u32* __restrict__ from = key_codes ? codes : idx;
+        for (u32 i = 0; i < key_w; ++i) {
+            const u32 e = i * 64u + lane, rr = e / key_w, j = e - rr * key_w;
+            const u32 sp = (u32)__shfl((int)c, (int)rr, 64);
+            if (rr < n_here) key[r0 * key_w + e] = j == 0u ? sp : from[((r0 + rr) * n_sp + sp) * w + (j - 1u)];
+        }
+    }
+}
+// the species column of an event list: entry pos[r] of every flagged read below the cap (the other columns: change_gather_kernel)
+__global__ __launch_bounds__(256) void call_species_gather_kernel(const u32* __restrict__ flag, const u32* __restrict__ pos, u32 n, u32 cap,
+                                                                  const u32* __restrict__ call_sp, u32* __restrict__ ev_sp) {
+    const u32 r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= n) return;
+    if (flag[r] != 0u && pos[r] < cap) ev_sp[pos[r]] = call_sp[r];
+}
+
 // =====================================================================================
 // launchers
 // =====================================================================================
@@ -5745,6 +5807,17 @@ void launch_change_events(hipStream_t st, const u32* flag, u32* pos, u32* bsum, 
     launch_count_scan(st, flag, pos, n, bsum);
     hipLaunchKernelGGL(change_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, flag, pos, n, cap, n_events, ev_read, idx, sum, w_idx,
                        idx ? ev_idx : nullptr, sum ? ev_sum : nullptr, codes, w_codes, codes ? ev_codes : nullptr);
+}
+void launch_species_call(hipStream_t st, const u32* idx, const u64* sum, const u32* codes, u32 ra, u32 rb, u32 n_sp, u32 top_k, u32 n_feat,
+                         u32* call_sp, u32* call_idx, u64* call_sum, u32* call_codes, u32* key, bool key_codes) {
+    if (rb <= ra || n_sp == 0 || top_k == 0) return;
+    if (!codes) { call_codes = nullptr; key_codes = false; }
+    hipLaunchKernelGGL(species_call_kernel, dim3(cdiv(rb - ra, 256)), dim3(256), 0, st, idx, sum, codes, ra, rb, n_sp, top_k, n_feat, call_sp,
+                       call_idx, call_sum, call_codes, key, key_codes ? 1u : 0u);
+}
+void launch_call_species_gather(hipStream_t st, const u32* flag, const u32* pos, u32 n, u32 cap, const u32* call_sp, u32* ev_sp) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(call_species_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, flag, pos, n, cap, call_sp, ev_sp);
 }
 void launch_window(hipStream_t st, const u64* lo, const u64* hi, u32 n_bt, const u64* q, const u32* n_q, u32* win, u32* h_nq) {
     hipLaunchKernelGGL(window_kernel, dim3(cdiv(n_bt, 256)), dim3(256), 0, st, lo, hi, n_bt, q, n_q, win, h_nq);

@@ -233,6 +233,15 @@ constexpr u32 kChangeWidthMax = 4096;
 void launch_change_flags(hipStream_t st, const u32* rows, u32 width, u32 ra, u32 rb, u32* flag);
 void launch_change_events(hipStream_t st, const u32* flag, u32* pos, u32* bsum, u32 n, u32 cap, u32* n_events, u32* ev_read,
                           const u32* idx, const u64* sum, u32 w_idx, u32* ev_idx, u64* ev_sum, const u32* codes, u32 w_codes, u32* ev_codes);
+// Species call of finished rows (skx_stream_bind_call, skx_stream_bind_call_changes, skx_call_rows): for the rows r in [ra, rb) of
+// idx / sum [.][n_sp][top_k] (and codes [.][n_sp][n_feat] or NULL) the species c(r) = lowest sp with the largest sum[r][sp][0], to
+// call_sp[r], and -- each optional -- that species' rows compact: call_idx / call_sum [.][top_k], call_codes [.][n_feat],
+// key [.][1 + (key_codes ? n_feat : top_k)] = {c(r), index row | codes}, the rows launch_change_flags compares.  Plain loads and stores,
+// one writer per element, launches over disjoint [ra, rb) share nothing.  n_sp, top_k >= 1.
+void launch_species_call(hipStream_t st, const u32* idx, const u64* sum, const u32* codes, u32 ra, u32 rb, u32 n_sp, u32 top_k, u32 n_feat,
+                         u32* call_sp, u32* call_idx, u64* call_sum, u32* call_codes, u32* key, bool key_codes);
+// behind launch_change_events over the key: ev_sp[pos[r]] = call_sp[r] for every flagged r < n with pos[r] < cap
+void launch_call_species_gather(hipStream_t st, const u32* flag, const u32* pos, u32 n, u32 cap, const u32* call_sp, u32* ev_sp);
 
 // dictionary
 // qrow (launch_classify) != NULL: pair_q receives ROWS of the bit matrix instead of positions in q

@@ -67,6 +67,16 @@ extern "C" int skx_ref_neighbours(const skx_ref* ref, uint32_t species, uint32_t
 // ... and the per-batch event list (`predict -s --changes`): without it the host finds the change points itself, over every read's rows.
 extern "C" int skx_stream_bind_changes(skx_stream* st, uint32_t cap, uint32_t* n_events, uint32_t* ev_read, uint32_t* ev_idx, uint64_t* ev_sum,
                                        uint32_t* ev_codes) __attribute__((weak));
+// ... and what `predict` with several -r stands on: the species resident together, the species call of a stream and of rows the host
+// holds.  There is no host route around these: without them several -r end with a message that names what is missing.
+extern "C" int skx_ref_create_multi(skx_ref** out, int device, uint32_t k, uint64_t seed, uint32_t s, uint32_t stride, uint32_t n_species,
+                                    const uint32_t* n_genomes, const uint64_t* const* hashes, const uint32_t* const* col_len) __attribute__((weak));
+extern "C" int skx_stream_bind_call(skx_stream* st, uint32_t* call_species, uint32_t* call_idx, uint64_t* call_sum, uint32_t* call_codes) __attribute__((weak));
+extern "C" int skx_stream_bind_call_changes(skx_stream* st, uint32_t cap, uint32_t* n_events, uint32_t* ev_read, uint32_t* ev_species,
+                                            uint32_t* ev_idx, uint64_t* ev_sum, uint32_t* ev_codes) __attribute__((weak));
+extern "C" int skx_call_rows(int device, const uint32_t* idx, const uint64_t* sum, const uint32_t* codes, uint64_t n_rows, uint32_t n_species,
+                             uint32_t top_k, uint32_t n_features, uint32_t* call_species, uint32_t* call_idx, uint64_t* call_sum,
+                             uint32_t* call_codes) __attribute__((weak));
 
 namespace sketchy {
 
@@ -110,6 +120,93 @@ class Sketchy {
         if (config.consensus) set_consensus_table(sketches, ref, geno, config);
         if (config.stream) sum_of_shared_hashes(fastx.empty() ? std::string("-") : fastx[0], sketches, ref, geno, config, out);
         else shared_hashes(fastx.empty() ? std::vector<std::string>{"-"} : fastx, sketches, ref, geno, config, out);
+    }
+
+    // `predict` with several -r (not in the reference, which takes one file and is run once per species): reference i goes with table i,
+    // all of them are resident together (skx_ref_create_multi), every read is sketched once, and after every read ONE species is
+    // called -- the lowest whose best genome has the largest sum (skx_stream_bind_call) -- whose rows or consensus are printed with
+    // the species' name (the file's name without directory and .msh) in a second field.
+    void predict_multi(const std::vector<std::string>& fastx, const std::vector<std::string>& references, const std::vector<std::string>& genotypes,
+                       const PredictConfig& config, std::ostream& out) {
+        if (config.stream && fastx.size() > 1) throw SketchyError("--stream takes one input");
+        if (config.consensus && config.top % 2 != 1) throw SketchyError("--top must be an odd number when using --consensus");
+        if (config.threads || config.timing || config.pin)  // (call_stream runs on this thread alone and keeps no timings)
+            std::fprintf(stderr, "sketchy-hip: warning: -j, --timing and --pin have no effect with several -r\n");
+        // (nothing is read and nothing is printed before the library is known to have what this mode stands on)
+        auto need = [](bool have, const char* name) {
+            if (!have) throw SketchyError(std::string("several -r need ") + name + ", which the loaded libsketchy_hip does not export");
+        };
+        need(skx_ref_create_multi != nullptr, "skx_ref_create_multi");
+        if (config.stream) need(skx_stream_bind_call != nullptr, "skx_stream_bind_call");
+        if (config.stream && config.changes) need(skx_stream_bind_call_changes != nullptr, "skx_stream_bind_call_changes");
+        if (!config.stream) { need(skx_call_rows != nullptr, "skx_call_rows"); need(skx_rank_sketches != nullptr, "skx_rank_sketches"); }
+        if (config.consensus) { need(skx_ref_set_genotypes != nullptr, "skx_ref_set_genotypes"); need(skx_consensus_rows != nullptr, "skx_consensus_rows"); }
+        if (references.size() > SKX_MAX_SPECIES) throw UsageError("at most " + std::to_string(SKX_MAX_SPECIES) + " references can be resident together");
+        std::vector<Species> species(references.size());
+        std::vector<std::vector<Sketch>> all;
+        size_t smallest = (size_t)-1;
+        for (size_t i = 0; i < references.size(); ++i) {
+            Species& sp = species[i];
+            auto sketches = read_sketch(references[i]);
+            if (sketches.empty()) throw SketchyError("reference sketch file " + references[i] + " holds no sketches");
+            sp.geno = read_genotypes(genotypes[i]);
+            for (const auto& s : sketches)
+                if (!sp.geno.map.count(s.name)) throw SketchyError("reference sketch " + s.name + " has no row in the genotype table " + genotypes[i]);
+            const auto slash = references[i].find_last_of('/');
+            sp.name = slash == std::string::npos ? references[i] : references[i].substr(slash + 1);
+            if (sp.name.size() > 4 && sp.name.compare(sp.name.size() - 4, 4, ".msh") == 0) sp.name.resize(sp.name.size() - 4);
+            const Sketch &a = all.empty() ? sketches[0] : all[0][0], &b = sketches[0];
+            if (a.kmer_length != b.kmer_length || a.hash_seed != b.hash_seed || a.hashes.size() != b.hashes.size())
+                throw UsageError("references " + references[0] + " and " + references[i] + " do not agree in k-mer size, seed and the size of their first sketch (" +
+                                 std::to_string(a.kmer_length) + "/" + std::to_string(a.hash_seed) + "/" + std::to_string(a.hashes.size()) + " and " +
+                                 std::to_string(b.kmer_length) + "/" + std::to_string(b.hash_seed) + "/" + std::to_string(b.hashes.size()) + ")");
+            smallest = std::min(smallest, sketches.size());
+            all.push_back(std::move(sketches));
+        }
+        if (config.top < 1 || config.top > smallest || config.top > SKX_MAX_TOP)
+            throw UsageError("--top must be between 1 and the number of sketches of the smallest reference = " + std::to_string(std::min<size_t>(smallest, SKX_MAX_TOP)));
+        // consensus: every (species, column) has its own dictionary of distinct strings in byte-wise sorted order; tables narrower than
+        // the widest are padded with code 0, and only a species' own columns are printed
+        size_t nfeat = 0;
+        std::vector<uint32_t> codes;
+        if (config.consensus) {
+            for (size_t i = 0; i < species.size(); ++i) {
+                Species& sp = species[i];
+                sp.nfeat = sp.geno.map.at(all[i][0].name).size();
+                for (const auto& s : all[i])
+                    if (sp.geno.map.at(s.name).size() != sp.nfeat) throw UsageError("genotype table " + genotypes[i] + " is ragged: --consensus with several -r needs as many columns in every row");
+                if (sp.nfeat < 1 || sp.nfeat > SKX_MAX_FEATURES)
+                    throw UsageError("genotype table " + genotypes[i] + " has " + std::to_string(sp.nfeat) + " columns: --consensus with several -r takes 1 to " + std::to_string(SKX_MAX_FEATURES));
+                nfeat = std::max(nfeat, sp.nfeat);
+            }
+            size_t total = 0, g0 = 0;
+            for (const auto& sk : all) total += sk.size();
+            codes.assign(total * nfeat, 0);
+            for (size_t i = 0; i < species.size(); ++i) {
+                Species& sp = species[i];
+                for (size_t j = 0; j < sp.nfeat; ++j) {
+                    std::map<std::string, uint32_t> rank;
+                    for (const auto& s : all[i]) rank.emplace(sp.geno.map.at(s.name)[j], 0u);
+                    std::vector<std::string> vals;
+                    for (auto& kv : rank) { kv.second = (uint32_t)vals.size(); vals.push_back(kv.first); }
+                    for (size_t g = 0; g < all[i].size(); ++g) codes[(g0 + g) * nfeat + j] = rank.at(sp.geno.map.at(all[i][g].name)[j]);
+                    sp.values.push_back(std::move(vals));
+                }
+                g0 += all[i].size();
+            }
+        } else {
+            for (size_t i = 0; i < species.size(); ++i)
+                for (const auto& s : all[i]) {
+                    species[i].mid.push_back("\t" + species[i].name + "\t" + s.name + "\t");
+                    species[i].tail.push_back("\t" + join_tab(species[i].geno.map.at(s.name)) + "\n");
+                }
+        }
+        if (config.header)
+            for (const auto& sp : species) out << "reads\t" << sp.name << "\tsketch_id\tshared_hashes\t" << sp.geno.header << "\n";
+        Ref ref(all, device_);
+        if (config.consensus) hip_check(skx_ref_set_genotypes(ref.h, (uint32_t)nfeat, codes.data()), "genotype table");
+        if (config.stream) call_stream(fastx.empty() ? std::string("-") : fastx[0], species, ref, nfeat, config, out);
+        else call_offline(fastx.empty() ? std::vector<std::string>{"-"} : fastx, species, ref, nfeat, config, out);
     }
 
     // `sketchy shared`: every reference x query pair, "ref query common" (src/sketchy.rs:251-276)
@@ -337,6 +434,32 @@ class Sketchy {
             if (s == 0) throw SketchyError("the first reference sketch is empty (it defines the read sketch size)");
             hip_check(skx_ref_create(&h, device, k, seed, s, stride, (uint32_t)sk.size(), flat.data(), len.data()), "reference upload");
         }
+        // several files resident together (skx_ref_create_multi); the caller has checked that they agree in k, seed and |sketch 0|
+        Ref(const std::vector<std::vector<Sketch>>& species, int device) {
+            k = species[0][0].kmer_length; seed = species[0][0].hash_seed; s = (uint32_t)species[0][0].hashes.size();
+            uint32_t stride = s;
+            for (const auto& sk : species)
+                for (const auto& x : sk) stride = std::max<uint32_t>(stride, (uint32_t)x.hashes.size());
+            if (s == 0) throw SketchyError("the first reference sketch is empty (it defines the read sketch size)");
+            std::vector<std::vector<uint64_t>> flat(species.size());
+            std::vector<std::vector<uint32_t>> len(species.size());
+            std::vector<uint32_t> n_genomes;
+            std::vector<const uint64_t*> hp;
+            std::vector<const uint32_t*> lp;
+            for (size_t sp = 0; sp < species.size(); ++sp) {
+                const auto& sk = species[sp];
+                flat[sp].assign((size_t)stride * sk.size(), ~0ull);
+                len[sp].resize(sk.size());
+                for (size_t g = 0; g < sk.size(); ++g) {
+                    std::copy(sk[g].hashes.begin(), sk[g].hashes.end(), flat[sp].begin() + g * (size_t)stride);
+                    len[sp][g] = (uint32_t)sk[g].hashes.size();
+                }
+                n_genomes.push_back((uint32_t)sk.size()); hp.push_back(flat[sp].data()); lp.push_back(len[sp].data());
+            }
+            stride_ = stride;
+            hip_check(skx_ref_create_multi(&h, device, k, seed, s, stride, (uint32_t)species.size(), n_genomes.data(), hp.data(), lp.data()),
+                      "reference upload");
+        }
         ~Ref() { skx_ref_destroy(h); }
         uint32_t stride_ = 0;
     };
@@ -495,6 +618,169 @@ class Sketchy {
         do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
         while (n) *p++ = tmp[--n];
         return p;
+    }
+
+    // ---- several references: the species call
+    struct Species {
+        std::string name;  // the reference file's name without directory and .msh
+        Genotypes geno;
+        std::vector<std::string> mid, tail;            // rows: per genome "\t<species>\t<sketch>\t" and "\t<genotype columns>\n"
+        size_t nfeat = 0;                              // consensus: the table's own columns ...
+        std::vector<std::vector<std::string>> values;  // ... and their dictionaries [column][code]
+    };
+    // the text of one read's call: `top` row lines of the called species, or its consensus line (codes: padded to the widest table;
+    // only the species' own columns are printed)
+    static void put_call(std::string& text, const std::vector<Species>& species, const PredictConfig& config, size_t read, uint32_t sp,
+                         const uint32_t* idx, const uint64_t* sum, const uint32_t* codes) {
+        char num[48];
+        const Species& s = species[sp];
+        if (config.consensus) {
+            text.append(num, (size_t)(put_u64(num, read) - num));
+            text += '\t'; text += s.name; text += "\t-\t-";
+            for (size_t j = 0; j < s.nfeat; ++j) { text += '\t'; text += s.values[j][codes[j]]; }
+            text += '\n';
+            return;
+        }
+        for (size_t t = 0; t < config.top; ++t) {
+            text.append(num, (size_t)(put_u64(num, read) - num));
+            text += s.mid[idx[t]];
+            text.append(num, (size_t)(put_u64(num, sum[t]) - num));
+            text += s.tail[idx[t]];
+        }
+    }
+    // what --changes compares: everything the call prints but the read number and the sums
+    static void call_key(std::string& key, const std::vector<Species>& species, const PredictConfig& config, uint32_t sp, const uint32_t* idx,
+                         const uint32_t* codes) {
+        key.assign(reinterpret_cast<const char*>(&sp), 4);
+        if (config.consensus) { key.append(reinterpret_cast<const char*>(codes), species[sp].nfeat * 4); return; }
+        for (size_t t = 0; t < config.top; ++t) { key += species[sp].mid[idx[t]]; key += species[sp].tail[idx[t]]; }
+    }
+
+    // streaming with several references: batches of -b reads through skx_stream_submit with the call bound and NO full rows -- 1 + top
+    // values per read come back instead of species x top -- over a ring of page-locked slots, in file order on this thread (the parse
+    // and format thread pools of the single-reference stream are not wired to this path).  --changes binds the call's event list
+    // (4 096 entries per batch) and formats events only; a batch with more than that is formatted from its full call, which is
+    // therefore bound to every batch in this mode too: 1 + top values per read still come back beside the events (an overflowing
+    // batch cannot be asked for again -- the table has moved on).  A block is dropped when its printed call -- species included --
+    // is the one printed last, across batches as within them.
+    void call_stream(const std::string& path, const std::vector<Species>& species, Ref& ref, size_t nfeat, const PredictConfig& config,
+                     std::ostream& out) {
+        const size_t cap_reads = std::max<size_t>(1, batch_), cap_bases = std::max<size_t>(1u << 20, cap_reads * 1600), top = config.top;
+        constexpr size_t kRing = 10;  // (one more than the batches the library holds between submit and rows: a wait returns at once)
+        constexpr size_t kChangesCap = 4096;
+        const size_t chg_cap = std::min(kChangesCap, cap_reads);
+        skx_stream* st = nullptr;
+        hip_check(skx_stream_create(&st, ref.h, (uint32_t)top, (uint32_t)cap_reads, cap_bases), "stream");
+        struct Guard { skx_stream* s; ~Guard() { skx_stream_destroy(s); } } guard{st};
+        struct CSlot {
+            uint8_t* bases = nullptr; uint64_t* offsets = nullptr;
+            uint32_t *sp = nullptr, *idx = nullptr, *codes = nullptr; uint64_t* sum = nullptr;
+            uint32_t *ev_n = nullptr, *ev_read = nullptr, *ev_sp = nullptr, *ev_idx = nullptr, *ev_codes = nullptr; uint64_t* ev_sum = nullptr;
+            size_t n = 0, first_read = 1; uint64_t ticket = 0; bool busy = false;
+        };
+        std::vector<CSlot> slots(kRing);
+        struct SlotGuard { std::vector<CSlot>& s; int dev; ~SlotGuard() { for (auto& x : s) for (void* p : {(void*)x.bases, (void*)x.offsets, (void*)x.sp, (void*)x.idx, (void*)x.codes, (void*)x.sum, (void*)x.ev_n, (void*)x.ev_read, (void*)x.ev_sp, (void*)x.ev_idx, (void*)x.ev_codes, (void*)x.ev_sum}) if (p) skx_host_free(dev, p); } } sguard{slots, device_};
+        auto pinned = [&](size_t bytes, const char* what) { void* p = nullptr; hip_check(skx_host_alloc(device_, &p, std::max<size_t>(bytes, 8)), what); return p; };
+        for (auto& sl : slots) {
+            sl.bases = static_cast<uint8_t*>(pinned(cap_bases, "batch buffer"));
+            sl.offsets = static_cast<uint64_t*>(pinned((cap_reads + 1) * 8, "batch buffer"));
+            sl.sp = static_cast<uint32_t*>(pinned(cap_reads * 4, "call buffer"));
+            if (config.consensus) sl.codes = static_cast<uint32_t*>(pinned(cap_reads * nfeat * 4, "call buffer"));
+            else { sl.idx = static_cast<uint32_t*>(pinned(cap_reads * top * 4, "call buffer")); sl.sum = static_cast<uint64_t*>(pinned(cap_reads * top * 8, "call buffer")); }
+            if (config.changes) {
+                sl.ev_n = static_cast<uint32_t*>(pinned(4, "event buffer"));
+                sl.ev_read = static_cast<uint32_t*>(pinned(chg_cap * 4, "event buffer"));
+                sl.ev_sp = static_cast<uint32_t*>(pinned(chg_cap * 4, "event buffer"));
+                if (config.consensus) sl.ev_codes = static_cast<uint32_t*>(pinned(chg_cap * nfeat * 4, "event buffer"));
+                else { sl.ev_idx = static_cast<uint32_t*>(pinned(chg_cap * top * 4, "event buffer")); sl.ev_sum = static_cast<uint64_t*>(pinned(chg_cap * top * 8, "event buffer")); }
+            }
+        }
+        std::string text, key, prev_key;
+        bool have_prev = false;
+        // a finished batch as text, in file order
+        auto emit = [&](CSlot& sl) {
+            hip_check(skx_stream_wait(st, sl.ticket), "wait");
+            sl.busy = false;
+            text.clear();
+            const bool events = config.changes && *sl.ev_n <= chg_cap;
+            const size_t m = events ? *sl.ev_n : sl.n;
+            for (size_t c = 0; c < m; ++c) {
+                const size_t r = events ? sl.ev_read[c] : c;
+                const uint32_t sp = events ? sl.ev_sp[c] : sl.sp[r];
+                const uint32_t* ri = config.consensus ? nullptr : (events ? sl.ev_idx + c * top : sl.idx + r * top);
+                const uint64_t* rs = config.consensus ? nullptr : (events ? sl.ev_sum + c * top : sl.sum + r * top);
+                const uint32_t* rc = config.consensus ? (events ? sl.ev_codes + c * nfeat : sl.codes + r * nfeat) : nullptr;
+                if (config.changes) {
+                    call_key(key, species, config, sp, ri, rc);
+                    if (have_prev && key == prev_key) continue;
+                    prev_key = key; have_prev = true;
+                }
+                put_call(text, species, config, sl.first_read + r, sp, ri, rs, rc);
+            }
+            out.write(text.data(), (std::streamsize)text.size());
+        };
+        FastxReader reader(path);
+        std::string seq;
+        bool more = true, carried = false;  // carried: seq holds a record that did not fit the batch before
+        size_t fed = 0, submitted = 0;
+        while (more) {
+            CSlot& sl = slots[submitted % kRing];
+            if (sl.busy) emit(sl);
+            size_t n = 0, bases = 0;
+            sl.offsets[0] = 0;
+            while (n < cap_reads && (!config.limit || fed + n < config.limit)) {
+                if (!carried && !(more = reader.next(seq))) break;
+                if (seq.size() > cap_bases) throw SketchyError("a record exceeds the batch buffer (" + std::to_string(cap_bases) + " bases): raise --batch");
+                carried = bases + seq.size() > cap_bases;
+                if (carried) break;
+                memcpy(sl.bases + bases, seq.data(), seq.size());
+                bases += seq.size();
+                sl.offsets[++n] = bases;
+            }
+            if (config.limit && fed + n >= config.limit) more = false;  // src/sketchy.rs:350-353
+            if (n == 0) break;
+            sl.n = n; sl.first_read = fed + 1;
+            hip_check(skx_stream_bind_call(st, sl.sp, sl.idx, sl.sum, sl.codes), "bind call");
+            if (config.changes) hip_check(skx_stream_bind_call_changes(st, (uint32_t)chg_cap, sl.ev_n, sl.ev_read, sl.ev_sp, sl.ev_idx, sl.ev_sum, sl.ev_codes), "bind call changes");
+            hip_check(skx_stream_submit(st, sl.bases, sl.offsets, (uint32_t)n, nullptr, nullptr, &sl.ticket), "submit");
+            sl.busy = true;
+            fed += n; ++submitted;
+        }
+        for (size_t k = 0; k < kRing; ++k) {  // what is still in the ring, oldest first
+            CSlot& o = slots[(submitted + k) % kRing];
+            if (o.busy) emit(o);
+        }
+        out.flush();
+    }
+
+    // offline with several references: one pooled sketch per sample, ranked against every species in one call (skx_rank_sketches is
+    // multi-species already), the species selected by skx_call_rows with shared hashes as the sums
+    void call_offline(const std::vector<std::string>& paths, const std::vector<Species>& species, Ref& ref, size_t nfeat,
+                      const PredictConfig& config, std::ostream& out) {
+        const size_t n = paths.size(), n_sp = species.size(), top = config.top;
+        std::vector<std::vector<uint64_t>> pooled(n);
+        std::vector<size_t> reads(n, 0);
+        pool_samples(paths, ref, config, pooled, reads);
+        size_t stride = 1;
+        for (const auto& p : pooled) stride = std::max(stride, p.size());
+        std::vector<uint64_t> flat(n * stride, 0);
+        std::vector<uint32_t> plen(n);
+        for (size_t f = 0; f < n; ++f) { std::copy(pooled[f].begin(), pooled[f].end(), flat.begin() + f * stride); plen[f] = (uint32_t)pooled[f].size(); }
+        std::vector<uint32_t> idx(n * n_sp * top), shared(n * n_sp * top), codes;
+        hip_check(skx_rank_sketches(ref.h, flat.data(), plen.data(), (uint32_t)n, (uint32_t)stride, (uint32_t)top, idx.data(), shared.data(), nullptr), "rank");
+        std::vector<uint64_t> sums(shared.begin(), shared.end());
+        if (config.consensus) {
+            codes.resize(n * n_sp * nfeat);
+            hip_check(skx_consensus_rows(ref.h, idx.data(), n, (uint32_t)top, codes.data()), "consensus");
+        }
+        std::vector<uint32_t> c_sp(n), c_idx(n * top), c_codes(config.consensus ? n * nfeat : 0);
+        std::vector<uint64_t> c_sum(n * top);
+        hip_check(skx_call_rows(device_, idx.data(), sums.data(), config.consensus ? codes.data() : nullptr, n, (uint32_t)n_sp, (uint32_t)top,
+                                (uint32_t)nfeat, c_sp.data(), c_idx.data(), c_sum.data(), config.consensus ? c_codes.data() : nullptr), "call");
+        std::string text;
+        for (size_t f = 0; f < n; ++f)
+            put_call(text, species, config, reads[f], c_sp[f], c_idx.data() + f * top, c_sum.data() + f * top, config.consensus ? c_codes.data() + f * nfeat : nullptr);
+        out.write(text.data(), (std::streamsize)text.size());
     }
 
     // streaming mode
@@ -970,6 +1256,13 @@ class Sketchy {
         const size_t n = paths.size(), n_ref = sketches.size();
         std::vector<std::vector<uint64_t>> pooled(n);
         std::vector<size_t> reads(n, 0);
+        pool_samples(paths, ref, config, pooled, reads);
+        rank_pooled(pooled, reads, sketches, n_ref, ref, geno, config, out);
+    }
+    // one pooled bottom-s sketch per sample, and the reads it was pooled from
+    void pool_samples(const std::vector<std::string>& paths, Ref& ref, const PredictConfig& config, std::vector<std::vector<uint64_t>>& pooled,
+                      std::vector<size_t>& reads) {
+        const size_t n = paths.size();
         Batch b; std::string seq;
         std::vector<uint64_t> sk, merged, valid; std::vector<uint32_t> len, first;
         for (size_t f = 0; f < n; ++f) {
@@ -991,6 +1284,10 @@ class Sketchy {
             }
             flush();
         }
+    }
+    void rank_pooled(const std::vector<std::vector<uint64_t>>& pooled, const std::vector<size_t>& reads, const std::vector<Sketch>& sketches,
+                     size_t n_ref, Ref& ref, const Genotypes& geno, const PredictConfig& config, std::ostream& out) {
+        const size_t n = pooled.size();
         size_t stride = 1;
         for (const auto& p : pooled) stride = std::max(stride, p.size());
         std::vector<uint64_t> flat(n * stride, 0);
@@ -1062,9 +1359,12 @@ static void usage() {
     std::fprintf(stderr,
                  "sketchy-hip sketch  -o OUT.msh [-i GENOME.fa[.gz] ...] [-s SIZE=1000] [-k K=16] [-e SEED=0] [--counts]   (paths on stdin without -i;\n"
                  "                    --counts: also write every hash's abundance, Mash's counts32)\n"
-                 "sketchy-hip predict -r REF.msh -g GENO.tsv [-i READS.fx[.gz] ...] [-t TOP] [-l LIMIT] [-s] [-c] [-H] [-x] [-b BATCH_READS] [-j THREADS] [--timing] [--pin]\n"
+                 "sketchy-hip predict -r REF.msh [...] -g GENO.tsv [...] [-i READS.fx[.gz] ...] [-t TOP] [-l LIMIT] [-s] [-c] [-H] [-x] [-b BATCH_READS] [-j THREADS] [--timing] [--pin]\n"
                  "                    (without -s: several inputs, one sample each -- the rows of every sample in input order; -l per input; -s: one input;\n"
                  "                    -x / --changes, with -s: only read 1 and the reads whose lines, the shared_hashes column aside, differ from the read before)\n"
+                 "                    several -r with as many -g (reference i goes with table i): all references resident together, and after every read the\n"
+                 "                    rows or consensus of ONE species -- the lowest whose best sketch has the largest sum -- with the species (the file's name\n"
+                 "                    without .msh) as second field; -H: one header line per reference\n"
                  "sketchy-hip neighbours -r REF.msh [-g GENO.tsv] [-t TOP=1] [-c] [-S] [-H]\n"
                  "                    (leave-one-out: per sketch of REF, in file order, the TOP other sketches that share the most hashes with it --\n"
                  "                    sketch_id neighbour_id shared_hashes [the neighbour's genotype columns]; -c, with -g and an odd TOP: one line per\n"
@@ -1079,6 +1379,7 @@ int main(int argc, char** argv) {
     if (argc < 2) { usage(); return 2; }
     const std::string cmd = argv[1];
     std::map<std::string, std::string> opt; std::map<std::string, bool> flag;
+    std::vector<std::string> references, tables;  // `predict -r` / `-g` take several files: reference i goes with table i
     std::vector<std::string> inputs;  // `sketch -i` takes several paths (src/cli.rs:27-28: multiple = true); so does offline `predict -i`
     const std::map<std::string, std::string> longnames = {{"--input", "-i"}, {"--reference", "-r"}, {"--genotypes", "-g"}, {"--top", "-t"}, {"--limit", "-l"},
                                                           {"--stream", "-s"}, {"--consensus", "-c"}, {"--header", "-H"}, {"--query", "-q"}, {"--params", "-p"},
@@ -1092,6 +1393,13 @@ int main(int argc, char** argv) {
         if (longnames.count(a)) a = longnames.at(a);
         // (predict: a lone "-" is a path -- stdin)
         if (many_inputs && a == "-i") { while (i + 1 < argc && (argv[i + 1][0] != '-' || (!is_sketch && !argv[i + 1][1]))) inputs.push_back(argv[++i]); continue; }
+        if (cmd == "predict" && (a == "-r" || a == "-g")) {
+            auto& list = a == "-r" ? references : tables;
+            if (i + 1 >= argc) { usage(); return 2; }
+            while (i + 1 < argc && argv[i + 1][0] != '-') list.push_back(argv[++i]);
+            if (!list.empty()) opt[a] = list[0];
+            continue;
+        }
         if ((!is_sketch && a == "-s") || a == "-c" || a == "-H" || a == "-p" || a == "-T" || a == "-P" || a == "-C" || a == "-x" || a == "-S") flag[a] = true;
         else if (i + 1 < argc) opt[a] = argv[++i];
         else { usage(); return 2; }
@@ -1112,6 +1420,11 @@ int main(int argc, char** argv) {
                        flag["-C"]);
         } else if (cmd == "predict") {
             if (!opt.count("-r") || !opt.count("-g")) { usage(); return 2; }
+            if (references.size() != tables.size()) {
+                std::fprintf(stderr, "Error: predict takes as many genotype tables (-g: %zu) as references (-r: %zu): reference i goes with table i\n",
+                             tables.size(), references.size());
+                return 2;
+            }
             if (flag["-x"] && !flag["-s"]) {
                 std::fprintf(stderr, "Error: predict --changes prints the change points of a stream: it needs -s\n");
                 return 2;
@@ -1125,7 +1438,8 @@ int main(int argc, char** argv) {
             cfg.limit = opt.count("-l") ? (size_t)std::atol(opt["-l"].c_str()) : 0;
             cfg.stream = flag["-s"]; cfg.consensus = flag["-c"]; cfg.header = flag["-H"]; cfg.changes = flag["-x"];
             cfg.threads = opt.count("-j") ? (size_t)std::max(1L, std::atol(opt["-j"].c_str())) : 0; cfg.timing = flag["-T"]; cfg.pin = flag["-P"];
-            app.predict(inputs, opt["-r"], opt["-g"], cfg, std::cout);
+            if (references.size() > 1) app.predict_multi(inputs, references, tables, cfg, std::cout);
+            else app.predict(inputs, opt["-r"], opt["-g"], cfg, std::cout);
         } else if (cmd == "neighbours") {
             if (!opt.count("-r")) { usage(); return 2; }
             sketchy::NeighboursConfig cfg;

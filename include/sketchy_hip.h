@@ -27,6 +27,8 @@
  *                             report only the reads at which what it would print (indices or consensus) differs from the read before
  *   skx_stream_bind_call / skx_stream_bind_call_changes / skx_call_rows <- no counterpart: the reference ranks against one file; these
  *                             say which of the resident species the sample is after every read, with that species' rows alone
+ *   skx_stream_enable_coverage / skx_stream_coverage[_rows|_rank] <- no counterpart: the reference keeps sums only; these say how many of
+ *                             a genome's own sketch hashes the reads have shared at least once (containment, as `mash screen` reports it)
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
  *   skx_sketch_groups      <- finch SketchScheme::{process x many, to_vec}: ONE sketcher fed several records -- all reads of an
  *                             offline `predict` (src/sketchy.rs:291-302), all contigs of a genome file in `sketch` (:473-478)
@@ -412,6 +414,37 @@ int skx_stream_reads(const skx_stream *st, uint64_t *n_reads);
 int skx_stream_stats(skx_stream *st, uint64_t *out, uint32_t n_out);
 /* rank the CURRENT table: first top_k of (sum desc, index asc) per species; idx/sum are host arrays [n_species][top_k] */
 int skx_stream_rank(skx_stream *st, uint32_t top_k, uint32_t *idx, uint64_t *sum);
+/*
+ * Breadth of a stream (no counterpart in the reference binary; what `mash screen` reports for a read set).  The running table is a sum:
+ * it grows with depth and counts repeats.  The breadth of genome g is
+ *   covered[g] = |{ h in column g : some read pushed so far has h in its bottom-s sketch }|
+ * -- truncation to s first, membership second, as for the sums.  covered[g] <= col_len[g] and <= table[g]; it never decreases, saturates at
+ * col_len[g], does not depend on how the reads are cut into batches, and covered[g] / col_len[g] is a containment in [0, 1] that compares
+ * across species and sketch sizes.
+ * skx_stream_enable_coverage gives the stream its SEEN set: one bit per distinct hash of the reference (per slot of the rare-hash index's key
+ * table, plus one each for 0xFFFFFFFFFFFFFFFE and 0xFFFFFFFFFFFFFFFF), zeroed.  The set belongs to the stream: streams on one reference are
+ * independent.  From then on every scoring pass of the stream marks its distinct query hashes that some genome holds (one small kernel behind
+ * the pass's dictionary; nothing of the table, the gains or the ranking is involved, rows and table are what they were).
+ *   SKX_ERR_INVALID      the stream has taken reads already (skx_stream_reads > 0): enable first, or after skx_stream_reset
+ *   SKX_ERR_UNSUPPORTED  the reference has no rare-hash index (policy "rare_hash_genomes" = 0): nothing gives a query hash a persistent
+ *                        identity there.  The stream is left exactly as it was and goes on working.
+ *   a second call on an enabled stream: SKX_OK, nothing changes
+ * skx_stream_reset clears the set and keeps coverage enabled; skx_stream_table_add and skx_stream_allreduce do not touch it (the sets of
+ * several ranks are not combined); skx_stream_destroy frees it.  A stream that never enables coverage allocates and launches nothing for it.
+ * The three queries flush pending batches (as skx_stream_table), wait for the marks of every queued pass and COUNT THEN: breadth is
+ * queried, not streamed per read.  A query walks the resident matrix against the set -- the columns of the genomes asked for, one probe of
+ * the key table per hash -- so _rows of a few genomes costs a fraction of the whole table:
+ *   skx_stream_coverage       covered [n_genomes] (host), species one after the other
+ *   skx_stream_coverage_rows  covered [n] for the global genome indices genomes[0..n) (any order, repeats allowed); n == 0: SKX_OK
+ *   skx_stream_coverage_rank  per species the first top_k of (covered desc, index asc): idx / covered [n_species][top_k], indices local to
+ *                             the species; top_k in 1..smallest species, independent of the stream's own top_k
+ * SKX_ERR_INVALID: a stream that never enabled coverage; and, before the device is touched, a NULL argument, an index >= n_genomes, top_k
+ * out of range.
+ */
+int skx_stream_enable_coverage(skx_stream *st);
+int skx_stream_coverage(skx_stream *st, uint32_t *covered);
+int skx_stream_coverage_rows(skx_stream *st, const uint32_t *genomes, uint32_t n, uint32_t *covered);
+int skx_stream_coverage_rank(skx_stream *st, uint32_t top_k, uint32_t *idx, uint32_t *covered);
 void skx_stream_destroy(skx_stream *st);
 
 /*

@@ -68,6 +68,10 @@ SYMBOLS = [
     ("skx_stream_reads", _i, [_vp, C.POINTER(_u64)]),
     ("skx_stream_stats", _i, [_vp, C.POINTER(_u64), _u32]),
     ("skx_stream_rank", _i, [_vp, _u32, _vp, _vp]),
+    ("skx_stream_enable_coverage", _i, [_vp]),
+    ("skx_stream_coverage", _i, [_vp, _vp]),
+    ("skx_stream_coverage_rows", _i, [_vp, _vp, _u32, _vp]),
+    ("skx_stream_coverage_rank", _i, [_vp, _u32, _vp, _vp]),
     ("skx_stream_destroy", None, [_vp]),
     ("skx_stream_set_profiling", _i, [_vp, _i]),
     ("skx_stream_profile", _i, [_vp, C.POINTER(C.c_double), C.POINTER(_u64)]),

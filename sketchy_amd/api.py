@@ -461,6 +461,31 @@ class SumOfSharedHashes:
         _lib.check(_lib.load().skx_stream_rank(self._h, top, _p(idx), _p(sm)))
         return idx, sm
 
+    def enable_coverage(self):
+        """Give the stream its seen set (skx_stream_enable_coverage): before the first read, or after reset()."""
+        _lib.check(_lib.load().skx_stream_enable_coverage(self._h))
+
+    def coverage(self) -> np.ndarray:
+        """covered[g] = hashes of genome g's column that some read so far has shared; uint32 [n_genomes], species one after the other."""
+        cov = np.zeros(self.ref.n_genomes, np.uint32)
+        _lib.check(_lib.load().skx_stream_coverage(self._h, _p(cov)))
+        return cov
+
+    def coverage_rows(self, genomes) -> np.ndarray:
+        """The same for a list of global genome indices (any order, repeats allowed)."""
+        genomes = np.ascontiguousarray(genomes, np.uint32).reshape(-1)
+        cov = np.zeros(len(genomes), np.uint32)
+        _lib.check(_lib.load().skx_stream_coverage_rows(self._h, _p(genomes), len(genomes), _p(cov)))
+        return cov
+
+    def coverage_rank(self, top):
+        """Per species the first `top` genomes of (covered desc, index asc): (idx, covered), each [n_species, top], indices local to the species."""
+        top = int(top)
+        shape = (self.ref.n_species, max(top, 0))
+        idx, cov = np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        _lib.check(_lib.load().skx_stream_coverage_rank(self._h, top, _p(idx), _p(cov)))
+        return idx, cov
+
     def consensus(self, top=None) -> np.ndarray:
         """Consensus codes of the CURRENT table: rank(top) followed by the reference's consensus_rows -> [F] / [n_species, F]."""
         idx, _ = self.rank(top)

@@ -1256,6 +1256,14 @@ struct skx_stream {
     u32* d_rank_idx = nullptr;  // [n_species][top] outputs of skx_stream_rank
     u64* d_rank_sum = nullptr;
     u32 rank_cap = 0;
+    // breadth of the stream (skx_stream_enable_coverage; all NULL until then): d_seen = one bit per slot of the reference's key table + two
+    // for the lifted hashes, marked on the scan stream behind every pass's classify; the queries' scratch: counts in padded order, the same
+    // widened for the ranking, outputs [n_genomes], {requested genomes, their 64-genome groups, their counts} [3][cov_list_cap], ranked rows [cov_rank_cap]
+    u32* d_seen = nullptr;
+    u32 seen_words = 0;
+    u32 *d_cov_pad = nullptr, *d_cov_out = nullptr, *d_cov_list = nullptr, *d_cov_ridx = nullptr;
+    u64 *d_cov_wide = nullptr, *d_cov_rsum = nullptr;
+    u32 cov_list_cap = 0, cov_rank_cap = 0;
     u32* h_poff = nullptr;   // pinned
     u64* h_offsets = nullptr;  // pinned
     // |Q| / pairs of the most recent pass whose dictionary has finished: the host only knows the pair count of a
@@ -1360,6 +1368,8 @@ static void stream_free(skx_stream* st) {
     for (int i = 1; i < skx_stream::kRankLanes; ++i)
         if (st->own_lane_stream && st->lane[i].s) (void)hipStreamDestroy(st->lane[i].s);
     for (void* p : ptrs) (void)hipFree(p);
+    for (void* p : {(void*)st->d_seen, (void*)st->d_cov_pad, (void*)st->d_cov_out, (void*)st->d_cov_list, (void*)st->d_cov_ridx,
+                    (void*)st->d_cov_wide, (void*)st->d_cov_rsum}) (void)hipFree(p);
     if (st->h_poff) (void)hipHostFree(st->h_poff);
     if (st->h_offsets) (void)hipHostFree(st->h_offsets);
     if (st->h_nq) (void)hipHostFree(st->h_nq);
@@ -2191,6 +2201,8 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
             // dense hashes -> rows [0, nd), what the scan looks for; the others -> the rows behind, filled from the genome lists
             skx::launch_classify(hs, d_q, d_nq, q_bound, st->rare_index(), st->d_qinfo, st->d_qloc, st->d_cls_bsum, st->d_qd, d_nd,
                                  st->d_qrow, st->d_sslot, st->h_nd + 2 * b);
+            // (a stream with coverage enabled: the pass's distinct hashes that some genome holds are SEEN -- by slot, as classify left them)
+            if (st->d_seen) skx::launch_seen_mark(hs, d_q, d_nq, q_bound, st->d_qinfo, st->d_seen, ref->kt_mask + 1u);
             scan_q = st->d_qd; scan_nq = d_nd;
         } else {
             skx::launch_nd_from_nq(hs, d_nq, d_nd, st->h_nd + 2 * b);
@@ -4151,6 +4163,7 @@ SKX_API int skx_stream_reset(skx_stream* st) {
     HIPCHK(hipStreamSynchronize(st->hs1));
     HIPCHK(hipStreamSynchronize(st->hs));
     HIPCHK(hipMemsetAsync(st->d_cum, 0, (size_t)st->ref->n_pad * 8, st->hs2));
+    if (st->d_seen) HIPCHK(hipMemsetAsync(st->d_seen, 0, (size_t)st->seen_words * 4, st->hs2));  // (a new sample has seen nothing; coverage stays enabled)
     HIPCHK(hipStreamSynchronize(st->hs2));
     st->reads_total = 0;
     st->h_nq[2] = 1; st->h_nq[3] = 1;  // (a new sample: every genome is a candidate again)
@@ -4209,6 +4222,131 @@ SKX_API int skx_stream_rank(skx_stream* st, uint32_t top_k, uint32_t* idx, uint6
     HIPCHK(hipMemcpyAsync(idx, st->d_rank_idx, rows * 4, hipMemcpyDeviceToHost, st->hs2));
     HIPCHK(hipMemcpyAsync(sum, st->d_rank_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
     HIPCHK(hipStreamSynchronize(st->hs2));
+    return SKX_OK;
+}
+
+// ------------------------------------------------------------------ breadth of a stream
+// covered[g] = hashes of genome g's column that were a shared hash of at least one read so far.  The marks of every pass run on the scan
+// stream (run_pass_multi, behind the pass's classify); the queries run there too, behind them, and walk the resident matrix against the
+// bitmap.  ONE walk kernel serves the whole table and a list of genomes: its unit of work is an aligned group of 64 padded genomes -- a
+// list launches the groups that hold a requested genome and nothing else (16 scattered genomes: 16 groups of the 625 at 40 000).
+SKX_API int skx_stream_enable_coverage(skx_stream* st) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (st->d_seen) return SKX_OK;
+    const skx_ref* ref = st->ref;
+    if (!ref->d_kt_key)
+        return fail(SKX_ERR_UNSUPPORTED, "skx_stream_enable_coverage: the reference has no rare-hash index (policy rare_hash_genomes = 0): nothing gives a "
+                                         "query hash a persistent identity");
+    uint64_t reads = 0;
+    SKXCHK(skx_stream_reads(st, &reads));
+    if (reads) return fail(SKX_ERR_INVALID, "skx_stream_enable_coverage: the stream has taken %llu reads already (enable it first, or after a reset)",
+                           (unsigned long long)reads);
+    SKXCHK(use_device(st->device));
+    const u32 words = (u32)(((u64)ref->kt_mask + 1u + 2u + 31u) / 32u);
+    u32 *seen = nullptr, *pad = nullptr, *out = nullptr;
+    u64* wide = nullptr;
+    hipError_t e = hipMalloc(&seen, (size_t)words * 4);
+    if (e == hipSuccess) e = hipMalloc(&pad, (size_t)ref->n_pad * 4);
+    if (e == hipSuccess) e = hipMalloc(&out, (size_t)ref->n_genomes * 4);
+    if (e == hipSuccess) e = hipMalloc(&wide, (size_t)ref->n_pad * 8);
+    if (e == hipSuccess) e = hipMemset(seen, 0, (size_t)words * 4);
+    if (e != hipSuccess) {  // (all or nothing: the stream is left as it was)
+        (void)hipFree(seen); (void)hipFree(pad); (void)hipFree(out); (void)hipFree(wide);
+        (void)hipGetLastError();
+        return fail(SKX_ERR_HIP, "skx_stream_enable_coverage: %s", hipGetErrorString(e));
+    }
+    st->d_cov_pad = pad; st->d_cov_out = out; st->d_cov_wide = wide; st->seen_words = words;
+    st->d_seen = seen;
+    return SKX_OK;
+}
+// count on the scan stream, behind the marks of every pass queued so far (the caller has flushed): groups == NULL -> every group of 64
+// padded genomes
+static int coverage_walk(skx_stream* st, const u32* d_groups, u32 n_groups) {
+    const skx_ref* ref = st->ref;
+    HIPCHK(hipMemsetAsync(st->d_cov_pad, 0, (size_t)ref->n_pad * 4, st->hs));
+    skx::launch_coverage_walk(st->hs, ref->d_mat, ref->s, d_groups, d_groups ? n_groups : ref->n_pad / 64u, ref->d_kt_key, ref->kt_mask, st->d_seen,
+                              ref->d_exc_g, ref->d_exc_h, ref->n_exc, st->d_cov_pad);
+    HIPCHK(hipGetLastError());
+    return SKX_OK;
+}
+SKX_API int skx_stream_coverage(skx_stream* st, uint32_t* covered) {
+    if (!st || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st->d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage: coverage was never enabled on this stream");
+    SKXCHK(use_device(st->device));
+    const skx_ref* ref = st->ref;
+    SKXCHK(flush_pending(st));
+    SKXCHK(coverage_walk(st, nullptr, 0));
+    skx::launch_coverage_gather(st->hs, st->d_cov_pad, ref->d_real2pad, nullptr, ref->n_genomes, st->d_cov_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(covered, st->d_cov_out, (size_t)ref->n_genomes * 4, hipMemcpyDeviceToHost, st->hs));
+    HIPCHK(hipStreamSynchronize(st->hs));
+    return SKX_OK;
+}
+SKX_API int skx_stream_coverage_rows(skx_stream* st, const uint32_t* genomes, uint32_t n, uint32_t* covered) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (!st->d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rows: coverage was never enabled on this stream");
+    if (n == 0) return SKX_OK;
+    if (!genomes || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
+    const skx_ref* ref = st->ref;
+    for (u32 i = 0; i < n; ++i)
+        if (genomes[i] >= ref->n_genomes) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rows: genomes[%u] = %u outside 0..n_genomes - 1 = %u", i, genomes[i], ref->n_genomes - 1);
+    SKXCHK(use_device(st->device));
+    // the aligned 64-genome groups (padded order) that hold a requested genome, each once
+    std::vector<u32> grp(n);
+    for (u32 i = 0; i < n; ++i) {
+        u32 sp = 0;
+        while (sp + 1 < ref->n_species && genomes[i] >= ref->sp_real0[sp + 1]) ++sp;
+        grp[i] = (ref->sp_g0[sp] + (genomes[i] - ref->sp_real0[sp])) / 64u;
+    }
+    std::sort(grp.begin(), grp.end());
+    grp.erase(std::unique(grp.begin(), grp.end()), grp.end());
+    SKXCHK(flush_pending(st));
+    if (n > st->cov_list_cap) {  // (list, groups and outputs: one allocation of three parts, grown to the longest list asked for)
+        HIPCHK(hipStreamSynchronize(st->hs));
+        (void)hipFree(st->d_cov_list);
+        st->d_cov_list = nullptr; st->cov_list_cap = 0;
+        const u32 cap = std::max<u32>(n, 64u);
+        HIPCHK(hipMalloc(&st->d_cov_list, (size_t)cap * 3 * 4));
+        st->cov_list_cap = cap;
+    }
+    u32 *d_grp = st->d_cov_list + st->cov_list_cap, *d_out = d_grp + st->cov_list_cap;
+    HIPCHK(hipMemcpyAsync(st->d_cov_list, genomes, (size_t)n * 4, hipMemcpyHostToDevice, st->hs));
+    HIPCHK(hipMemcpyAsync(d_grp, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, st->hs));
+    int rc = coverage_walk(st, d_grp, (u32)grp.size());
+    if (rc == SKX_OK) {
+        skx::launch_coverage_gather(st->hs, st->d_cov_pad, ref->d_real2pad, st->d_cov_list, n, d_out);
+        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(covered, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, st->hs) != hipSuccess)
+            rc = fail(SKX_ERR_HIP, "skx_stream_coverage_rows: %s", hipGetErrorString(hipGetLastError()));
+    }
+    const hipError_t e = hipStreamSynchronize(st->hs);  // (`genomes` and the group list are only borrowed until here, on every way out)
+    if (rc == SKX_OK && e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_stream_coverage_rows: %s", hipGetErrorString(e));
+    return rc;
+}
+SKX_API int skx_stream_coverage_rank(skx_stream* st, uint32_t top_k, uint32_t* idx, uint32_t* covered) {
+    if (!st || !idx || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st->d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rank: coverage was never enabled on this stream");
+    const skx_ref* ref = st->ref;
+    if (top_k < 1 || top_k > ref->min_species) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rank: top_k=%u outside 1..%u (the smallest species)", top_k, ref->min_species);
+    SKXCHK(use_device(st->device));
+    const size_t rows = (size_t)ref->n_species * top_k;
+    SKXCHK(flush_pending(st));
+    if (rows > st->cov_rank_cap) {
+        HIPCHK(hipStreamSynchronize(st->hs));
+        (void)hipFree(st->d_cov_ridx); (void)hipFree(st->d_cov_rsum);
+        st->d_cov_ridx = nullptr; st->d_cov_rsum = nullptr; st->cov_rank_cap = 0;
+        HIPCHK(hipMalloc(&st->d_cov_ridx, rows * 4));
+        HIPCHK(hipMalloc(&st->d_cov_rsum, rows * 8));
+        st->cov_rank_cap = (u32)rows;
+    }
+    SKXCHK(coverage_walk(st, nullptr, 0));
+    skx::launch_coverage_widen(st->hs, st->d_cov_pad, ref->n_pad, st->d_cov_wide);
+    skx::launch_rank_table(st->hs, st->d_cov_wide, ref->species(), top_k, st->d_cov_ridx, st->d_cov_rsum);
+    HIPCHK(hipGetLastError());
+    std::vector<u64> sum(rows);
+    HIPCHK(hipMemcpyAsync(idx, st->d_cov_ridx, rows * 4, hipMemcpyDeviceToHost, st->hs));
+    HIPCHK(hipMemcpyAsync(sum.data(), st->d_cov_rsum, rows * 8, hipMemcpyDeviceToHost, st->hs));
+    HIPCHK(hipStreamSynchronize(st->hs));
+    for (size_t i = 0; i < rows; ++i) covered[i] = (u32)sum[i];
     return SKX_OK;
 }
 

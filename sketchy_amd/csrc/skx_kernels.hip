@@ -4360,6 +4360,100 @@ __global__ void gather_table_kernel(const u64* __restrict__ cum, u64* __restrict
 }
 
 // =====================================================================================
+// breadth of a stream: which reference hashes has any read shared so far (skx_stream_enable_coverage)
+// =====================================================================================
+// The state is one bit per slot of the reference's key table (the rare-hash index: every hash of the matrix is a key) plus two bits behind
+// them for the lifted hashes kEmpty and kEmpty + 1, owned by the stream.  seen_mark_kernel runs behind a pass's classify_a_kernel, which
+// has left qinfo[i] = key-table slot of Q[i] (or kSlotNone: no genome holds it): one lane per distinct query hash of the pass, one
+// atomicOr per hash some genome holds (different hashes share a word; the old value is not used).  Q holds what the reads' bottom-s
+// sketches hold -- truncation came first -- and setting a bit twice changes nothing, so a pass replayed batch by batch marks the same bits.
+__global__ __launch_bounds__(256) void seen_mark_kernel(const u64* __restrict__ q, const u32* __restrict__ n_q, u32 q_bound,
+                                                        const u32* __restrict__ qinfo, u32* __restrict__ seen, u32 kt_slots) {
+    const u32 nq = min(*n_q, q_bound), i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= nq) return;
+    const u64 h = q[i];
+    u32 bit;
+    if (h >= kEmpty) bit = kt_slots + (u32)(h - kEmpty);
+    else {
+        const u32 slot = qinfo[i];
+        if (slot == kSlotNone || slot >= kt_slots) return;
+        bit = slot;
+    }
+    const u32 m = 1u << (bit & 31u);
+    if (!(seen[bit >> 5] & m)) atomicOr(&seen[bit >> 5], m);  // (most hashes of a deep sample were seen long ago: a load instead of an atomic)
+}
+// The query side: covered[p] = hashes of padded genome p whose bit is set.  A workgroup takes one aligned group of 64 padded genomes
+// (groups[blockIdx.x], or blockIdx.x itself when groups == NULL: the whole table) and kCovRanks ranks of it; lanes run along the genome
+// axis, so a wave reads one rank of its 64 genomes in 512 contiguous bytes (the matrix is mat[tile][rank][256 genomes], see
+// ref_tile_kernel / ref_rows_kernel), wave w the ranks r0 + 4 j + w.  Every entry below kEmpty is a key of the table: the probe
+// (classify_a_kernel's: kt_start, linear) always ends on it; entries >= kEmpty are padding and are never probed.  Four ranks per lane are
+// in flight at a time -- the probes are dependent gathers into a table of tens of MB (beyond an XCD's L2, inside the Infinity Cache), the
+// bitmap behind them is 1/64 of that.  The genomes of a clonal collection mostly hold the same hash at the same rank, so the lanes of a
+// wave mostly ask for the same lines.
+// The block of rank chunk 0 also adds what the matrix does not hold: the genome's lifted hashes (exc_g ascending by padded genome, as
+// ref_rows_tail_kernel reads it) against the two lifted bits.  One atomicAdd per genome and block into covered (zero on entry).
+constexpr u32 kCovRanks = 256;
+__global__ __launch_bounds__(256) void coverage_walk_kernel(const u64* __restrict__ mat, u32 s, const u32* __restrict__ groups,
+                                                            const u64* __restrict__ key, u32 mask, const u32* __restrict__ seen,
+                                                            const u32* __restrict__ exc_g, const u64* __restrict__ exc_h, u32 n_exc,
+                                                            u32* __restrict__ covered) {
+    __shared__ u32 part[4][64];
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u32 p = (groups ? groups[blockIdx.x] : blockIdx.x) * 64u + lane;  // (64 | 256: the group lies inside one tile)
+    const u64* col = mat + (size_t)(p / kTileGenomes) * s * kTileGenomes + p % kTileGenomes;
+    const u32 r0 = blockIdx.y * kCovRanks, r1 = min(s, r0 + kCovRanks);
+    u32 n = 0;
+    for (u32 r = r0 + wv; r < r1; r += 16u) {
+        u64 h[4];
+        u32 slot[4];
+#pragma unroll
+        for (u32 j = 0; j < 4u; ++j) {
+            const u32 rr = r + 4u * j;
+            h[j] = rr < r1 ? col[(size_t)rr * kTileGenomes] : kPad;
+        }
+#pragma unroll
+        for (u32 j = 0; j < 4u; ++j) slot[j] = kt_start(h[j], mask);
+#pragma unroll
+        for (u32 j = 0; j < 4u; ++j) {
+            if (h[j] >= kEmpty) continue;
+            u32 sl = slot[j], tries = 0;
+            for (;;) {
+                const u64 kk = key[sl];
+                if (kk == h[j]) { n += (seen[sl >> 5] >> (sl & 31u)) & 1u; break; }
+                if (kk == kPad || ++tries > mask) break;  // (cannot happen: every stored hash is a key)
+                sl = (sl + 1u) & mask;
+            }
+        }
+    }
+    if (blockIdx.y == 0 && wv == 0 && n_exc) {
+        u32 a = 0, b = n_exc;  // first exception of a genome >= p
+        while (a < b) {
+            const u32 mid = (a + b) >> 1;
+            if (exc_g[mid] < p) a = mid + 1; else b = mid;
+        }
+        const u32 lifted = seen[(mask + 1u) >> 5] >> ((mask + 1u) & 31u);  // (the table has a power of two of slots, at least 32: both bits in one word)
+        for (; a < n_exc && exc_g[a] == p; ++a) n += (lifted >> (u32)(exc_h[a] - kEmpty)) & 1u;
+    }
+    part[wv][lane] = n;
+    __syncthreads();
+    if (wv == 0) {
+        const u32 t = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
+        if (t) atomicAdd(&covered[p], t);
+    }
+}
+// the padded counts as the caller sees them: out[i] = covered[real2pad[genomes ? genomes[i] : i]]
+__global__ void coverage_gather_kernel(const u32* __restrict__ covered, const u32* __restrict__ real2pad, const u32* __restrict__ genomes, u32 n,
+                                       u32* __restrict__ out) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = covered[real2pad[genomes ? genomes[i] : i]];
+}
+// ... and widened for rank_table_kernel, which ranks a padded u64 table in (value desc, index asc) order
+__global__ void coverage_widen_kernel(const u32* __restrict__ covered, u32 n_pad, u64* __restrict__ wide) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_pad) wide[i] = covered[i];
+}
+
+// =====================================================================================
 // the table without the ranking, and the genomes a batch's ranking has to look at (round 5)
 // =====================================================================================
 // Rounds 1-4 took the running table out of the ranking chain: per-segment increments, chunk sums, prefixes -- every pair's 64-byte
@@ -6092,6 +6186,23 @@ void launch_add_table(hipStream_t st, u64* cum, const u64* add, u32 n_real, cons
 }
 void launch_gather_table(hipStream_t st, const u64* cum, u64* out, u32 n_real, const u32* real2pad) {
     hipLaunchKernelGGL(gather_table_kernel, dim3(cdiv(n_real, 256)), dim3(256), 0, st, cum, out, n_real, real2pad);
+}
+void launch_seen_mark(hipStream_t st, const u64* q, const u32* n_q, u32 q_bound, const u32* qinfo, u32* seen, u32 kt_slots) {
+    if (q_bound == 0) return;
+    hipLaunchKernelGGL(seen_mark_kernel, dim3(cdiv(q_bound, 256)), dim3(256), 0, st, q, n_q, q_bound, qinfo, seen, kt_slots);
+}
+void launch_coverage_walk(hipStream_t st, const u64* mat, u32 s, const u32* groups, u32 n_groups, const u64* key, u32 mask, const u32* seen,
+                          const u32* exc_g, const u64* exc_h, u32 n_exc, u32* covered) {
+    if (n_groups == 0 || s == 0) return;
+    hipLaunchKernelGGL(coverage_walk_kernel, dim3(n_groups, cdiv(s, kCovRanks)), dim3(256), 0, st, mat, s, groups, key, mask, seen, exc_g, exc_h,
+                       n_exc, covered);
+}
+void launch_coverage_gather(hipStream_t st, const u32* covered, const u32* real2pad, const u32* genomes, u32 n, u32* out) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(coverage_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, covered, real2pad, genomes, n, out);
+}
+void launch_coverage_widen(hipStream_t st, const u32* covered, u32 n_pad, u64* wide) {
+    hipLaunchKernelGGL(coverage_widen_kernel, dim3(cdiv(n_pad, 256)), dim3(256), 0, st, covered, n_pad, wide);
 }
 
 // =====================================================================================

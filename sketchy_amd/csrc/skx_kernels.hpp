@@ -390,6 +390,16 @@ void launch_ref_rows(hipStream_t st, const u64* mat, u32 s, u32 p0, u32 cnt, con
 void launch_unpad_rows(hipStream_t st, const u32* cnt, u32 n_rows, u32 n_pad, u32 n_real, const u32* real2pad, u32* out);
 void launch_add_table(hipStream_t st, u64* cum, const u64* add, u32 n_real, const u32* real2pad);
 void launch_gather_table(hipStream_t st, const u64* cum, u64* out, u32 n_real, const u32* real2pad);
+// ---- breadth of a stream (skx_kernels.hip, "breadth of a stream").  seen: one bit per key-table slot + two for the lifted hashes,
+// (kt_slots + 2 + 31) / 32 words.  launch_seen_mark: behind launch_classify of the same pass, same stream (q, n_q, q_bound, qinfo: its).
+void launch_seen_mark(hipStream_t st, const u64* q, const u32* n_q, u32 q_bound, const u32* qinfo, u32* seen, u32 kt_slots);
+// covered[p] += seen hashes of padded genome p, for the genomes of the aligned 64-genome groups groups[0 .. n_groups) (NULL: groups
+// 0 .. n_groups - 1, the whole table); covered [n_pad], zero on entry for those genomes
+void launch_coverage_walk(hipStream_t st, const u64* mat, u32 s, const u32* groups, u32 n_groups, const u64* key, u32 mask, const u32* seen,
+                          const u32* exc_g, const u64* exc_h, u32 n_exc, u32* covered);
+// out[i] = covered[real2pad[genomes ? genomes[i] : i]], i < n;  wide[p] = covered[p], p < n_pad (for launch_rank_table)
+void launch_coverage_gather(hipStream_t st, const u32* covered, const u32* real2pad, const u32* genomes, u32 n, u32* out);
+void launch_coverage_widen(hipStream_t st, const u32* covered, u32 n_pad, u64* wide);
 
 // ---- pooled sketches (skx_kernels.hip, "pooled sketches"): the bottom-s distinct hashes of the union of a group's rows
 // One round of the segmented merge tree: items[i] = {left row, partner row or 0xFFFFFFFF (no partner: the row is copied)}; rows are

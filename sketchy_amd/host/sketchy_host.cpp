@@ -77,6 +77,10 @@ extern "C" int skx_stream_bind_call_changes(skx_stream* st, uint32_t cap, uint32
 extern "C" int skx_call_rows(int device, const uint32_t* idx, const uint64_t* sum, const uint32_t* codes, uint64_t n_rows, uint32_t n_species,
                              uint32_t top_k, uint32_t n_features, uint32_t* call_species, uint32_t* call_idx, uint64_t* call_sum,
                              uint32_t* call_codes) __attribute__((weak));
+// ... and the breadth of a stream (`screen`).  No host route either: the seen set lives on the device, beside the stream.
+extern "C" int skx_stream_enable_coverage(skx_stream* st) __attribute__((weak));
+extern "C" int skx_stream_coverage(skx_stream* st, uint32_t* covered) __attribute__((weak));
+extern "C" int skx_stream_table(skx_stream* st, uint64_t* cum) __attribute__((weak));  // (`screen` is the host's only reader of the table)
 
 namespace sketchy {
 
@@ -313,6 +317,75 @@ class Sketchy {
                 if (with_geno) out << "\t" << join_tab(geno.map.at(name));
                 out << "\n";
             }
+        }
+    }
+
+    // `screen` (not in the reference; what `mash screen` answers): how much of every reference sketch is in the read set.  All reads go
+    // through one table-only stream (top_k = 0: no per-read ranking) with coverage enabled; then, per sketch, covered = its hashes that
+    // some read shared, containment = covered / its own size, and the running sum from the table.  The `top` best by containment
+    // (ties: the sketch earlier in the file) are printed.  One reference only: several -r are not built.
+    void screen(const std::string& fastx, const std::string& reference, const std::string& genotypes, size_t top, size_t limit, bool header,
+                std::ostream& out) {
+        // there is no host route to the number: a library without the entry points ends here, before anything is read
+        if (!skx_stream_enable_coverage) throw SketchyError("screen needs skx_stream_enable_coverage, which the loaded libsketchy_hip does not export");
+        if (!skx_stream_coverage) throw SketchyError("screen needs skx_stream_coverage, which the loaded libsketchy_hip does not export");
+        if (!skx_stream_table) throw SketchyError("screen needs skx_stream_table, which the loaded libsketchy_hip does not export");
+        const auto sketches = read_sketch(reference);
+        const size_t n = sketches.size();
+        if (n == 0) throw SketchyError("reference sketch file holds no sketches");
+        if (top < 1 || top > n) throw UsageError("--top must be between 1 and the number of reference sketches = " + std::to_string(n));
+        const bool with_geno = !genotypes.empty();
+        Genotypes geno;
+        if (with_geno) {
+            geno = read_genotypes(genotypes);
+            for (const auto& s : sketches)
+                if (!geno.map.count(s.name)) throw SketchyError("reference sketch " + s.name + " has no row in the genotype table");
+        }
+        Ref ref(sketches, device_);
+        const uint64_t max_bases = 1ull << 28;
+        skx_stream* st = nullptr;
+        hip_check(skx_stream_create(&st, ref.h, 0, (uint32_t)batch_, max_bases), "stream");
+        std::vector<uint32_t> covered(n);
+        std::vector<uint64_t> sum(n);
+        try {
+            hip_check(skx_stream_enable_coverage(st), "screen");
+            FastxReader reader(fastx);
+            Batch b; std::string seq;
+            size_t reads = 0;
+            auto flush = [&]() {
+                if (b.n() == 0) return;
+                hip_check(skx_stream_push(st, b.bases.data(), b.offsets.data(), (uint32_t)b.n(), nullptr, nullptr, nullptr, nullptr, nullptr), "screen");
+                b.clear();
+            };
+            while (reader.next(seq)) {
+                if (b.n() && b.bases.size() + seq.size() > max_bases) flush();
+                b.add(seq); ++reads;
+                if (b.n() == batch_) flush();
+                if (reads == limit) break;
+            }
+            flush();
+            hip_check(skx_stream_coverage(st, covered.data()), "screen");
+            hip_check(skx_stream_table(st, sum.data()), "screen");
+        } catch (...) {
+            skx_stream_destroy(st);
+            throw;
+        }
+        skx_stream_destroy(st);
+        // by containment = covered / size, compared as fractions (exact); an empty sketch contains nothing
+        std::vector<uint32_t> order(n);
+        for (size_t g = 0; g < n; ++g) order[g] = (uint32_t)g;
+        auto size_of = [&](uint32_t g) { return (uint64_t)sketches[g].hashes.size(); };
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+            return (uint64_t)covered[x] * std::max<uint64_t>(size_of(y), 1) > (uint64_t)covered[y] * std::max<uint64_t>(size_of(x), 1);
+        });
+        if (header) out << "sketch_id\tcovered\tsketch_size\tcontainment\tshared_hashes" << (with_geno ? "\t" + geno.header : std::string()) << "\n";
+        char buf[32];
+        for (size_t j = 0; j < top; ++j) {
+            const uint32_t g = order[j];
+            std::snprintf(buf, sizeof buf, "%.6f", size_of(g) ? (double)covered[g] / (double)size_of(g) : 0.0);
+            out << sketches[g].name << "\t" << covered[g] << "\t" << size_of(g) << "\t" << buf << "\t" << sum[g];
+            if (with_geno) out << "\t" << join_tab(geno.map.at(sketches[g].name));
+            out << "\n";
         }
     }
 
@@ -1370,6 +1443,10 @@ static void usage() {
                  "                    sketch_id neighbour_id shared_hashes [the neighbour's genotype columns]; -c, with -g and an odd TOP: one line per\n"
                  "                    sketch, the consensus of its neighbours; -S / --summary, with -g: one line per genotype column -- column, the\n"
                  "                    sketches whose own value is that consensus, all sketches)\n"
+                 "sketchy-hip screen  -r REF.msh -i READS.fx[.gz] [-g GENO.tsv] [-t TOP=10] [-l LIMIT] [-H]\n"
+                 "                    (containment of every sketch of REF in the read set: the TOP sketches by covered / sketch_size --\n"
+                 "                    sketch_id covered sketch_size containment shared_hashes [genotype columns]; covered = hashes of the sketch that\n"
+                 "                    at least one read shared; one reference: several -r are not built)\n"
                  "sketchy-hip shared  -r REF.msh -q QUERY.msh\n"
                  "sketchy-hip info    -i SKETCH.msh [-p]\n"
                  "sketchy-hip check   -r REF.msh -g GENO.tsv\n");
@@ -1456,6 +1533,11 @@ int main(int argc, char** argv) {
             }
             cfg.top = (size_t)top;
             app.neighbours(opt["-r"], opt.count("-g") ? opt["-g"] : std::string(), cfg, std::cout);
+        } else if (cmd == "screen") {
+            if (!opt.count("-r") || !opt.count("-i")) { usage(); return 2; }
+            const long top = opt.count("-t") ? std::atol(opt["-t"].c_str()) : 10, limit = opt.count("-l") ? std::atol(opt["-l"].c_str()) : 0;
+            if (top < 1) { std::fprintf(stderr, "Error: --top must be at least 1\n"); return 2; }
+            app.screen(opt["-i"], opt["-r"], opt.count("-g") ? opt["-g"] : std::string(), (size_t)top, (size_t)std::max(0L, limit), flag["-H"], std::cout);
         } else if (cmd == "shared") {
             if (!opt.count("-r") || !opt.count("-q")) { usage(); return 2; }
             app.shared(opt["-r"], opt["-q"], std::cout);

@@ -1080,6 +1080,9 @@ struct skx_stream {
     u32* h_nd = nullptr;     // page-locked: [2 b] = |Q| of buffer set b's latest pass, [2 b + 1] = its dense rows
     // ---- the table without the ranking, the candidates of a batch (skx_kernels.hip; scan stream unless said otherwise)
     u32 *d_rowcnt = nullptr;     // [kPassBatchesMax][qcap] occurrences of every row among a batch's pairs
+    skx::SlotExtents rowcnt_ext; // the rows of it a batch slot's last use dirtied
+    bool front_open = false;     // a deferred pass began its front half and did not get to its end (an error in between): extents unknown
+    void extents_unknown() { rowcnt_ext.whole(); for (auto& q : ps) { q.smap_ext.whole(); q.mqc_whole = 0xFFu; } }
     u32 *d_gain = nullptr;       // [kPassBatchesMax][n_pad]
     u32 *d_gain_s = nullptr;     // the rare rows' part: [kPassBatchesMax][n_pad] entries gain_sparse_stride() words apart (references with the index)
     u32 *d_candslot = nullptr;   // [kPassBatchesMax][n_pad] candidate slot of a genome (or none)
@@ -1112,6 +1115,9 @@ struct skx_stream {
         u64 *tabc = nullptr;     // [kPassBatchesMax][n_pad_c] the candidates' start values
         u32 *ncand = nullptr;    // [kPassBatchesMax][n_species]
         u32 *mode = nullptr, *any_full = nullptr, *nqc_total = nullptr;
+        u32 *ext = nullptr;      // [kPassBatchesMax] rows of mqc / rowany_c a batch slot's last use dirtied (behind nqc_total, same allocation)
+        skx::SlotExtents smap_ext;  // ... and of smap (host: the pass's row stride bounds them)
+        u32 mqc_whole = 0xFFu;   // batch slots whose compact matrices are to be cleared whole whatever ext says (never cleared yet, reset, failed pass)
         u64 *mc = nullptr;       // [kPassBatchesMax][kCandRows / 64][n_pad_c] the candidates' columns of M (dense words)
         u64 *mqc = nullptr;      // [kPassBatchesMax][n_grp_c][kCandRows][8] their group-major matrices
         u64 *rowany_c = nullptr; // [kPassBatchesMax][n_grp_c][kCandRows / 64]
@@ -1890,6 +1896,7 @@ static int stream_create_internal(skx_stream** out, const skx_ref* ref, u32 top_
             SCHK(hipMalloc(&q.tabc, (size_t)nb * st->n_pad_c * 8));
             SCHK(hipMalloc(&q.ncand, (size_t)nb * n_sp * 4));
             SCHK(hipMalloc(&q.mode, 64)); SCHK(hipMalloc(&q.any_full, 64)); SCHK(hipMalloc(&q.nqc_total, 64));
+            q.ext = q.nqc_total + skx::kPassBatchesMax;  // (nothing known yet: mqc_whole says so until a pass has published the slot's extent)
             SCHK(hipMemset(q.any_full, 0, 64));
             SCHK(hipMalloc(&q.mc, (size_t)nb * (rows_c / 64) * st->n_pad_c * 8));
             SCHK(hipMalloc(&q.mqc, (size_t)nb * st->n_grp_c * rows_c * skx::kRankWords * 8));
@@ -2057,6 +2064,8 @@ static int grow_query_rows(skx_stream* st, u64 want_rows) {
         (void)hipFree(st->ps[i].smap); st->ps[i].smap = sm[i];
     }
     (void)hipFree(st->d_rowcnt); st->d_rowcnt = cnt;
+    st->rowcnt_ext.whole();  // (fresh allocations are not zero: the next use of every slot clears all of it)
+    for (auto& q : st->ps) q.smap_ext.whole();
     if (lrow) { (void)hipFree(st->d_lrow); st->d_lrow = lrow; }
     st->qcap = (u32)rows;
     st->mq_stride[0] = st->mq_stride[1] = 0;
@@ -2308,22 +2317,9 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
         HIPCHK(hipGetLastError());
         return SKX_OK;
     };
+    // (everything these kernels want zero on entry: pass_clear, at the head of the deferred block below)
     auto row_counts = [&]() -> int {
-        HIPCHK(hipMemset2DAsync(st->d_rowcnt, (size_t)qstride * 4, 0, (size_t)nq_rows * 4, (size_t)n_sub, hs));
         skx::launch_pass_hist(hs, d_pair_q, pbt, st->d_rowcnt, qstride);
-        if (split_dict) HIPCHK(hipMemsetAsync(st->d_gain_s, 0, (size_t)n_sub * n_pad * 4 * skx::gain_sparse_stride(), hs));
-        if (long_rows) {  // the rows with a bit row: listed per batch (by the short lists' walk), added up with bit-sliced counters
-            HIPCHK(hipMemsetAsync(st->d_nlrow, 0, skx::pass_counter_bytes(), hs));
-            if (st->d_inb) {
-                HIPCHK(hipMemsetAsync(st->d_inb, 0, (size_t)n_sub * ref->n_lw * 8, hs));
-                HIPCHK(hipMemsetAsync(st->d_hit, 0, (size_t)n_sub * ref->n_lw * 8, hs));
-            }
-            HIPCHK(hipMemsetAsync(st->d_gain_l, 0, (size_t)n_sub * n_pad * 4, hs));
-            if (st->use_pat) {
-                HIPCHK(hipMemsetAsync(st->d_hist, 0, (size_t)n_sub * st->npat_pad * 4, hs));
-                HIPCHK(hipMemsetAsync(st->d_nprow, 0, skx::pass_counter_bytes(), hs));
-            }
-        }
         return SKX_OK;
     };
     const u32 n_words = nq_rows / 64;
@@ -2385,7 +2381,73 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
         Span sp(st, 4, hs);
         const u32 n_sp = ref->n_species, cap = skx::kCandCap, rows_c = skx::kCandRows;
         const u64* m_int = split ? st->d_mint : nullptr;
-        HIPCHK(hipMemsetAsync(st->d_gain, 0, (size_t)n_sub * n_pad * 4, hs));
+        // candidates.  A batch that wants the per-read x per-genome debug matrix ranks on everything; so does every batch when the
+        // experiment knob SKX_CAND=0 says so
+        static const int cand_env = skx::knob("SKX_CAND") ? atoi(skx::knob("SKX_CAND")) : 1;
+        static const int hint_env = skx::knob("SKX_CAND_HINT") ? atoi(skx::knob("SKX_CAND_HINT")) : 1;  // experiment knob: 0 = never predict
+        (void)hint_env;
+        all_forced = !cand_env;
+        u32 force_full = all_forced ? 0xFFu : 0u;
+        for (int i = 0; i < n_sub; ++i) if (subs[i].d_shared || subs[i].d_counts) force_full |= 1u << i;
+        const bool pat_rows = st->use_pat && long_rows && ranked && P > 0 && !all_forced;
+        const bool fill_mqc = ranked && split_dict && P > 0 && !all_forced;  // (the compact matrices get their rare rows this pass)
+        const u32 n_gw = n_pad / 64;
+        // ---- ONE clear for the whole front half: every array its kernels want zero (d_cbase: all-ones) on entry, where a dozen and a
+        // half memsets -- two of them 2D -- sat between them.  Hoisting them here changes no order that matters:
+        //  * the st->d_* scratch (row counts, gains, lists' counters, candidate masks and words) is read and written on THIS stream
+        //    only, by the front half of a pass: the previous pass's front half is complete in stream order, and nothing between here
+        //    and a clear's former place reads the array it cleared;
+        //  * the ps.* arrays belong to buffer set b, whose last readers are the ranking chains of the pass two back: wait_back above
+        //    made this stream wait for them (ev_back[b] / back_pending[b]); the FIFO of two passes (queue_chains_until at the top)
+        //    means they were queued at all.  The former clears sat behind the same wait.
+        // The per-row arrays are cleared as far as their slot's last use could have dirtied them (rowcnt_ext / smap_ext: that pass's row
+        // stride; the compact matrices: ps.ext[], left on the device by that pass's cand_publish) -- beyond that they are clean.
+        {
+            if (st->front_open) st->extents_unknown();  // (a pass that failed half-way: what it dirtied is anybody's guess)
+            st->front_open = true;
+            skx::PassClear pcl;
+            bool ok = skx::clear_add(pcl, st->d_gain, (size_t)n_sub * n_pad * 4);
+            if (P > 0) {
+                ok = ok && skx::clear_add_slots(pcl, st->d_rowcnt, qstride, st->rowcnt_ext, (u32)n_sub);
+                st->rowcnt_ext.used((u32)n_sub, nq_rows);
+                if (split_dict) ok = ok && skx::clear_add(pcl, st->d_gain_s, (size_t)n_sub * n_pad * 4 * skx::gain_sparse_stride());
+                if (long_rows) {  // the rows with a bit row: listed per batch (by the short lists' walk), added up with bit-sliced counters
+                    ok = ok && skx::clear_add(pcl, st->d_nlrow, skx::pass_counter_bytes());
+                    if (st->d_inb) {
+                        ok = ok && skx::clear_add(pcl, st->d_inb, (size_t)n_sub * ref->n_lw * 8);
+                        ok = ok && skx::clear_add(pcl, st->d_hit, (size_t)n_sub * ref->n_lw * 8);
+                    }
+                    ok = ok && skx::clear_add(pcl, st->d_gain_l, (size_t)n_sub * n_pad * 4);
+                    if (st->use_pat) {
+                        ok = ok && skx::clear_add(pcl, st->d_hist, (size_t)n_sub * st->npat_pad * 4);
+                        ok = ok && skx::clear_add(pcl, st->d_nprow, skx::pass_counter_bytes());
+                    }
+                }
+            }
+            ok = ok && skx::clear_add(pcl, st->d_cbad, 64);
+            pcl.nqc = st->d_nqc; pcl.nqc_words = skx::pass_counter_bytes() / 4; pcl.nqc_stride = skx::pass_counter_stride();
+            pcl.nqc_start = pat_rows ? st->npat_pad : 0u;  // (the mapped rare rows come behind the patterns' rows)
+            if (ranked) {
+                ok = ok && skx::clear_add(pcl, st->d_candmask, (size_t)n_pad * 4);
+                ok = ok && skx::clear_add(pcl, ps.grp_any_c, (size_t)n_sub * st->n_grp_c * 4);
+                if (fill_mqc) {
+                    pcl.mqc = ps.mqc; pcl.rowany_c = ps.rowany_c; pcl.ext = ps.ext;
+                    pcl.n_b = (u32)n_sub; pcl.n_grp_c = st->n_grp_c; pcl.rows_c = rows_c; pcl.whole_mask = ps.mqc_whole;
+                    ps.mqc_whole &= ~((1u << n_sub) - 1u);  // (this pass's cand_publish leaves the slots' extents)
+                    ok = ok && skx::clear_add_slots(pcl, ps.smap, qstride, ps.smap_ext, (u32)n_sub);
+                    ps.smap_ext.used((u32)n_sub, nq_rows);
+                    if (long_rows) {  // the candidates by genome word (cand_words)
+                        ok = ok && skx::clear_add(pcl, st->d_cw, (size_t)n_sub * n_gw * 8);
+                        ok = ok && skx::clear_add(pcl, st->d_cbase, (size_t)n_sub * n_gw * 4, 0xFFu);
+                        ok = ok && skx::clear_add(pcl, st->d_ncwl, 64);
+                    }
+                }
+            } else {
+                ok = ok && skx::clear_add(pcl, ps.ncand, (size_t)n_sub * n_sp * 4);
+            }
+            if (!ok) return fail(SKX_ERR_HIP, "internal: the pass's clear table is full or a range is not word-aligned");
+            skx::launch_pass_clear(hs, pcl);
+        }
         if (P > 0) {
             SKXCHK(row_counts());
             skx::launch_gain_dense(hs, d_m, m_int, n_pad, d_nd, sdm ? ref->n_sd : q_bound, st->d_rowcnt, qstride, (u32)n_sub, st->d_gain,
@@ -2395,35 +2457,14 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
         skx::launch_pass_tables(hs, st->d_cum, st->d_gain, (split_dict && P > 0) ? st->d_gain_s : nullptr,
                                 (long_rows && P > 0) ? st->d_gain_l : nullptr, (u32)n_sub, n_pad, ps.tab);
         st->d_cum = ps.tab + (size_t)n_sub * n_pad;  // (readers: the next pass on this stream; everybody else behind ev_front / a flush)
-        // candidates.  A batch that wants the per-read x per-genome debug matrix ranks on everything; so does every batch when the
-        // experiment knob SKX_CAND=0 says so
-        static const int cand_env = skx::knob("SKX_CAND") ? atoi(skx::knob("SKX_CAND")) : 1;
-        static const int hint_env = skx::knob("SKX_CAND_HINT") ? atoi(skx::knob("SKX_CAND_HINT")) : 1;  // experiment knob: 0 = never predict
-        (void)hint_env;
-        all_forced = !cand_env;
-        u32 force_full = all_forced ? 0xFFu : 0u;
-        for (int i = 0; i < n_sub; ++i) if (subs[i].d_shared || subs[i].d_counts) force_full |= 1u << i;
-        HIPCHK(hipMemsetAsync(st->d_cbad, 0, 64, hs));
-        HIPCHK(hipMemsetAsync(st->d_nqc, 0, skx::pass_counter_bytes(), hs));
-        const bool pat_rows = st->use_pat && long_rows && ranked && P > 0 && !all_forced;
-        if (pat_rows) skx::launch_pat_nqc_init(hs, st->d_nqc, st->npat_pad);  // (the mapped rare rows come behind the patterns' rows)
         if (ranked) {
-            HIPCHK(hipMemsetAsync(st->d_candmask, 0, (size_t)n_pad * 4, hs));
             skx::launch_cand_select(hs, ps.tab, n_pad, spc, (u32)n_sub, st->top_k, cap, ps.cand, st->d_candslot, ps.tabc, ps.ncand, st->d_cbad,
                                     st->d_candmask);
-            HIPCHK(hipMemsetAsync(ps.grp_any_c, 0, (size_t)n_sub * st->n_grp_c * 4, hs));
-            if (split_dict && P > 0 && !all_forced) {
-                HIPCHK(hipMemsetAsync(ps.mqc, 0, (size_t)n_sub * st->n_grp_c * rows_c * skx::kRankWords * 8, hs));
-                HIPCHK(hipMemsetAsync(ps.rowany_c, 0, (size_t)n_sub * st->n_grp_c * (rows_c / 64) * 8, hs));
-                HIPCHK(hipMemset2DAsync(ps.smap, (size_t)qstride * 4, 0, (size_t)nq_rows * 4, (size_t)n_sub, hs));
+            if (fill_mqc) {
                 skx::launch_cand_sparse(hs, st->d_sslot, d_nd, q_bound, st->rare_index(), st->d_candmask, st->d_candslot, n_pad, st->d_cbad, (u32)n_sub, st->d_nqc,
                                         ps.smap, qstride, ps.mqc, (size_t)st->n_grp_c * rows_c * skx::kRankWords, rows_c, ps.rowany_c,
                                         st->n_grp_c * (rows_c / 64), ps.grp_any_c, st->n_grp_c, walk_scale);
                 if (long_rows) {  // ... and the rows with a bit row: ANDed with the candidates' words
-                    const u32 n_gw = n_pad / 64;
-                    HIPCHK(hipMemsetAsync(st->d_cw, 0, (size_t)n_sub * n_gw * 8, hs));
-                    HIPCHK(hipMemsetAsync(st->d_cbase, 0xFF, (size_t)n_sub * n_gw * 4, hs));
-                    HIPCHK(hipMemsetAsync(st->d_ncwl, 0, 64, hs));
                     skx::launch_cand_words(hs, ps.cand, st->n_pad_c, (u32)n_sub, n_gw, st->d_cw, st->d_cbase, st->d_cwl, st->d_ncwl);
                     if (st->d_hit) skx::launch_cand_hit(hs, ps.cand, st->n_pad_c, (u32)n_sub, st->d_cbad, st->rare_index(), st->d_inb, st->d_hit);
                     skx::launch_cand_long(hs, st->long_rows(), st->rare_index(), d_nd, st->d_cw, st->d_cbase, st->d_cwl, st->d_ncwl, st->n_pad_c,
@@ -2440,12 +2481,11 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
                                              ps.rowany_c, st->n_grp_c * (rows_c / 64), ps.grp_any_c, st->n_grp_c, q_bound, walk_scale);
                 }
             }
-        } else {
-            HIPCHK(hipMemsetAsync(ps.ncand, 0, (size_t)n_sub * n_sp * 4, hs));
         }
         seq = ++st->cand_seq;
         skx::launch_cand_publish(hs, st->d_cbad, force_full, ps.ncand, st->d_nqc, d_nd, (u32)n_sub, n_sp, rows_c, ps.mode, ps.any_full,
-                                 ps.nqc_total, ps.h_pub, seq);
+                                 ps.nqc_total, ps.h_pub, seq, fill_mqc ? ps.ext : nullptr);
+        st->front_open = false;
         if (ranked && P > 0 && !all_forced)
             skx::launch_cand_gather_m(hs, d_m, m_int, n_pad, d_nd, sdm ? ref->n_sd : q_bound, ps.cand, st->n_pad_c, st->d_cbad, (u32)n_sub, ps.mc, rows_c / 64);
         only_if = ps.any_full;
@@ -4173,6 +4213,7 @@ SKX_API int skx_stream_reset(skx_stream* st) {
     st->lcount_floor = st->lcount_seq;
     st->fresh_table = true;
     st->cum_writer = nullptr;          // (everything is synchronised)
+    st->extents_unknown();             // (a new sample: its first passes clear whole slots once, as every pass did before the extents)
     return SKX_OK;
 }
 SKX_API int skx_stream_reads(const skx_stream* st, uint64_t* n_reads) {

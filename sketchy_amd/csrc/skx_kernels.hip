@@ -4881,9 +4881,36 @@ __global__ __launch_bounds__(256) void cand_long_kernel(LongRows lr, RareIndex r
 // (one wave per (pattern, batch) walks the pattern's list -- its representative's genome list -- once per pass; pcw[b][p][word] keeps the
 // words for the rows below).  A row of the pass whose list is pattern + exceptions then needs no row of its own unless one of its
 // exceptions is a candidate of the batch: smap -> the pattern's row; else a new row = the pattern's words with those bits flipped.
-// The mapped rows start behind the patterns': the pass's nqc counters start at n_pat rounded up to 64 (pat_nqc_init_kernel).
-__global__ void pat_nqc_init_kernel(u32* __restrict__ nqc, u32 v) {
-    if (threadIdx.x < kPassBatchesMax) nqc[threadIdx.x * kCtrStride] = v;
+// The mapped rows start behind the patterns': the pass's nqc counters start at n_pat rounded up to 64 (pass_clear_kernel).
+
+// ---- everything a deferred pass wants zero (or all-ones) before its front half, in ONE launch (skx_pass_clear.hpp): the table of
+// ranges arrives by value (kernel arguments: scalar loads, no copy), every range is filled grid-stride with 16-byte stores -- the
+// few words in front of and behind the aligned part one by one.  The compact matrices are cleared up to the row extent their last
+// use left in ext[] (cand_publish_kernel), or whole.
+__device__ __forceinline__ void fill_words(u32* __restrict__ p, u64 n, u32 v, u64 tid, u64 n_thr) {
+    const u64 head = min(n, (u64)(((16u - (u32)((size_t)p & 15u)) & 15u) >> 2));
+    if (tid < head) p[tid] = v;
+    uint4* q = reinterpret_cast<uint4*>(p + head);
+    const u64 nv = (n - head) >> 2, tail = (n - head) & 3ull;
+    const uint4 vv = make_uint4(v, v, v, v);
+    for (u64 i = tid; i < nv; i += n_thr) q[i] = vv;
+    if (tid < tail) p[head + nv * 4ull + tid] = v;
+}
+__global__ __launch_bounds__(256) void pass_clear_kernel(PassClear pc) {
+    const u64 tid = (u64)blockIdx.x * 256u + threadIdx.x, n_thr = (u64)gridDim.x * 256u;
+    for (u32 k = 0; k < pc.n; ++k) fill_words(static_cast<u32*>(pc.r[k].p), pc.r[k].bytes >> 2, pc.r[k].fill ? 0xFFFFFFFFu : 0u, tid, n_thr);
+    if (pc.nqc && tid < pc.nqc_words) pc.nqc[tid] = (tid % pc.nqc_stride == 0ull) ? pc.nqc_start : 0u;
+    if (pc.mqc) {
+        const u32 rows_c = pc.rows_c;
+        for (u32 i = 0; i < pc.n_b; ++i) {
+            const u32 e = ((pc.whole_mask >> i) & 1u) ? rows_c : min(pc.ext[i], rows_c);
+            for (u32 grp = 0; grp < pc.n_grp_c; ++grp) {
+                const size_t at = (size_t)i * pc.n_grp_c + grp;
+                fill_words(reinterpret_cast<u32*>(pc.mqc + at * rows_c * kRankWords), (u64)e * kRankWords * 2u, 0u, tid, n_thr);
+                fill_words(reinterpret_cast<u32*>(pc.rowany_c + at * (rows_c >> 6)), (u64)((e + 63u) >> 6) * 2u, 0u, tid, n_thr);
+            }
+        }
+    }
 }
 __global__ __launch_bounds__(256) void cand_pat_rows_kernel(RareIndex ri, const u32* __restrict__ n_d, const u32* __restrict__ candmask,
                                                             const u32* __restrict__ candslot, u32 n_pad, u32* __restrict__ bad,
@@ -5292,7 +5319,7 @@ __global__ __launch_bounds__(256) void cand_sparse_kernel(const u32* __restrict_
 // batch needs the full bit matrix (the transpose of M and the fill of its rare rows only run then), sequence number last
 __global__ void cand_publish_kernel(const u32* __restrict__ bad, u32 force_full, const u32* __restrict__ ncand, const u32* __restrict__ nqc,
                                     const u32* __restrict__ n_d, u32 n_b, u32 n_sp, u32 rows_c, u32* __restrict__ mode, u32* __restrict__ any_full,
-                                    u32* __restrict__ nqc_total, volatile u32* __restrict__ h_pub, u32 seq) {
+                                    u32* __restrict__ nqc_total, volatile u32* __restrict__ h_pub, u32 seq, u32* __restrict__ ext) {
     __builtin_amdgcn_s_setprio(3);
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     u32 any = 0;
@@ -5304,6 +5331,9 @@ __global__ void cand_publish_kernel(const u32* __restrict__ bad, u32 force_full,
         u32 mx = 0;
         for (u32 s_ = 0; s_ < n_sp; ++s_) mx = max(mx, ncand[b * n_sp + s_]);
         nqc_total[b] = nd64 + nqc[b * kCtrStride];   // rows of the compact problem (dense rows, padded to 64, + the mapped rare rows)
+        // (ext, passes that filled the compact matrices: the rows this use dirtied -- what pass_clear_kernel clears at the slot's next
+        // use; a batch whose matrix overflowed: all of them)
+        if (ext) ext[b] = bad[b] != 0u ? rows_c : min(rows_c, nd64 + nqc[b * kCtrStride]);
         h_pub[b] = full ? 0u : 1u;
         h_pub[kPassBatchesMax + b] = mx;
     }
@@ -5770,7 +5800,14 @@ void launch_pat_matrix(hipStream_t st, const u64* mlong, const u32* pat_rep, u32
 }
 u32 pat_record_words() { return kPatRec; }
 u32 pat_words_max() { return kPatWords; }
-void launch_pat_nqc_init(hipStream_t st, u32* nqc, u32 v) { hipLaunchKernelGGL(pat_nqc_init_kernel, dim3(1), dim3(64), 0, st, nqc, v); }
+void launch_pass_clear(hipStream_t st, const PassClear& pc) {
+    // (16-byte stores, at least four per thread of the whole-array ranges; at most four workgroups per CU: the fill is bound by HBM writes)
+    u64 bytes = pc.mqc ? (u64)pc.n_b * pc.n_grp_c * 4096u * 64u : 0u;
+    for (u32 k = 0; k < pc.n; ++k) bytes += pc.r[k].bytes;
+    const u32 blocks = (u32)std::min<u64>(1024u, std::max<u64>(16u, bytes / (256u * 64u)));
+    hipLaunchKernelGGL(pass_clear_kernel, dim3(blocks), dim3(256), 0, st, pc);
+}
+u32 pass_counter_stride() { return kCtrStride; }
 void launch_cand_pat_rows(hipStream_t st, const RareIndex& ri, const u32* n_d, const u32* candmask, const u32* candslot, u32 n_pad, u32* bad, u32 n_b,
                           u64* pcw, u64* mqc, size_t mqc_stride, u32 rows_c, u64* rowany_c, u32 rowany_stride, u32* grp_any_c, u32 n_grp_c) {
     if (ri.n_pat == 0) return;
@@ -5837,9 +5874,9 @@ void launch_cand_sparse(hipStream_t st, const u32* sslot, const u32* n_d, u32 ro
                        candslot, n_pad, bad, n_b, nqc, smap, smap_stride, mqc, mqc_stride, rows_c, rowany_c, rowany_stride, grp_any_c, n_grp_c);
 }
 void launch_cand_publish(hipStream_t st, const u32* bad, u32 force_full, const u32* ncand, const u32* nqc, const u32* n_d, u32 n_b, u32 n_sp,
-                         u32 rows_c, u32* mode, u32* any_full, u32* nqc_total, u32* h_pub, u32 seq) {
+                         u32 rows_c, u32* mode, u32* any_full, u32* nqc_total, u32* h_pub, u32 seq, u32* ext) {
     hipLaunchKernelGGL(cand_publish_kernel, dim3(1), dim3(1), 0, st, bad, force_full, ncand, nqc, n_d, n_b, n_sp, rows_c, mode, any_full, nqc_total,
-                       h_pub, seq);
+                       h_pub, seq, ext);
 }
 void launch_m_clear(hipStream_t st, u64* m_bits, u64* m_int, u32 n_pad, const u32* n_d, const u32* any_full) {
     hipLaunchKernelGGL(m_clear_kernel, dim3(512), dim3(256), 0, st, m_bits, m_int, n_pad, n_d, any_full);

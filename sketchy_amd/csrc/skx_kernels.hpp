@@ -6,6 +6,8 @@
 
 #include <stdlib.h>
 
+#include "skx_pass_clear.hpp"
+
 namespace skx {
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -165,6 +167,11 @@ static const u32 kPassBatchesMax = 8;          // batches of a pass (stream_coal
 static const u32 kCandCap = 1024;              // candidates per species the compact ranking takes (two rank groups)
 static const u32 kCandRows = 131072;           // rows of a compact bit matrix (dense rows + the rare rows some candidate holds)
 struct PassBatches { u32 n; u32 p_off[kPassBatchesMax + 1]; };  // pairs [p_off[b], p_off[b + 1]) of the pass's lists are batch b's
+// every "zero on entry" below, for a whole deferred pass, in one launch: the ranges of pc (skx_pass_clear.hpp), the nqc counters' start
+// values, the compact matrices up to the rows their last use dirtied (ext[], which launch_cand_publish writes)
+static_assert(kClearSlotsMax == kPassBatchesMax, "one extent per batch slot");
+void launch_pass_clear(hipStream_t st, const PassClear& pc);
+u32 pass_counter_stride();  // u32 words between two per-batch counters (pass_counter_bytes() in all)
 // cnt[b][row] (zero on entry; row_stride entries per batch) = occurrences of the row among batch b's pairs
 void launch_pass_hist(hipStream_t st, const u32* pair_q, const PassBatches& pb, u32* cnt, u32 row_stride);
 // gain[b][g] (zero on entry) += sum over rows of cnt[b][row] * (row's bit for g): dense rows from m_bits (BEFORE the transpose
@@ -178,11 +185,10 @@ void launch_gain_dense(hipStream_t st, const u64* m_bits, const u64* m_int /* or
 // (pr: the rows whose list is pattern + exceptions add to hist / gain_x and are listed for launch_cand_pat_map; hist, gain_x, nprow zero on entry)
 void launch_gain_sparse(hipStream_t st, const u32* n_d, u32 rows_bound, const u32* cnt, u32 row_stride, u32 n_b, u32 n_pad, u32* gain_s,
                         const u32* sslot, const RareIndex& ri, const LongRows* lr, u32 walk_scale, const PatRows* pr = nullptr);
-// pattern rows of the compact problems: nqc starts at n_pat rounded up to 64 (the mapped rows come behind the patterns' rows);
+// pattern rows of the compact problems: nqc starts at n_pat rounded up to 64 (the mapped rows come behind the patterns' rows: PassClear::nqc_start);
 // launch_cand_pat_rows: row n_d[2] + p of mqc[b] = pattern p at batch b's candidates, pcw[b][p][n_grp_c * 8] the same words;
 // launch_cand_pat_map: smap of every listed pattern row -> its pattern's row, or a new row (pattern's words with the exceptions that are
 // candidates flipped)
-void launch_pat_nqc_init(hipStream_t st, u32* nqc, u32 v);
 void launch_cand_pat_rows(hipStream_t st, const RareIndex& ri, const u32* n_d, const u32* candmask, const u32* candslot, u32 n_pad, u32* bad, u32 n_b,
                           u64* pcw, u64* mqc, size_t mqc_stride, u32 rows_c, u64* rowany_c, u32 rowany_stride, u32* grp_any_c, u32 n_grp_c);
 void launch_cand_pat_map(hipStream_t st, const LongRows& lr, const PatRows& pr, const RareIndex& ri, const u32* n_d, const u32* candmask,
@@ -211,7 +217,8 @@ void launch_cand_sparse(hipStream_t st, const u32* sslot, const u32* n_d, u32 ro
 // mode[b] = 1 compact / 0 everything, *any_full, nqc_total[b] = rows of the compact problem; h_pub (page-locked): [b] mode,
 // [8 + b] largest candidate count, [16] any_full, [18] = n_b, [17] = seq (written last)
 void launch_cand_publish(hipStream_t st, const u32* bad, u32 force_full, const u32* ncand, const u32* nqc, const u32* n_d, u32 n_b, u32 n_sp,
-                         u32 rows_c, u32* mode, u32* any_full, u32* nqc_total, u32* h_pub, u32 seq);
+                         u32 rows_c, u32* mode, u32* any_full, u32* nqc_total, u32* h_pub, u32 seq,
+                         u32* ext = nullptr /* [n_b] rows of mqc[b] this pass dirtied (passes that filled the compact matrices) */);
 void launch_m_clear(hipStream_t st, u64* m_bits, u64* m_int /* or NULL */, u32 n_pad, const u32* n_d, const u32* any_full);
 void launch_cand_pair_rows(hipStream_t st, const u32* pair_q, u32 n_pairs, const u32* n_d, const u32* smap, u32 rows_c, u32* pair_qc);
 void launch_cand_rows_back(hipStream_t st, u32* out_idx, u32 n_reads, u32 n_sp, u32 top_k, const u32* cand, u32 cap, const u32* g0);

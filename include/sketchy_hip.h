@@ -29,6 +29,8 @@
  *                             say which of the resident species the sample is after every read, with that species' rows alone
  *   skx_stream_enable_coverage / skx_stream_coverage[_rows|_rank] <- no counterpart: the reference keeps sums only; these say how many of
  *                             a genome's own sketch hashes the reads have shared at least once (containment, as `mash screen` reports it)
+ *   skx_stream_enable_depth / skx_stream_depth[_rows|_count|_export|_import] <- no counterpart: how OFTEN each of a genome's hashes was
+ *                             shared (the median multiplicity of `mash screen`), and the counters as portable (hash, count) pairs
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
  *   skx_sketch_groups      <- finch SketchScheme::{process x many, to_vec}: ONE sketcher fed several records -- all reads of an
  *                             offline `predict` (src/sketchy.rs:291-302), all contigs of a genome file in `sketch` (:473-478)
@@ -445,6 +447,46 @@ int skx_stream_enable_coverage(skx_stream *st);
 int skx_stream_coverage(skx_stream *st, uint32_t *covered);
 int skx_stream_coverage_rows(skx_stream *st, const uint32_t *genomes, uint32_t n, uint32_t *covered);
 int skx_stream_coverage_rank(skx_stream *st, uint32_t top_k, uint32_t *idx, uint32_t *covered);
+/*
+ * Depth of a stream (no counterpart in the reference binary; the median-multiplicity column of `mash screen`).  Breadth says whether a
+ * genome is there, not how deep: a containment of 0.95 reads the same from 40 reads and from 4 million, and a contaminant seen once per
+ * hash reads the same as the main strain seen fifty times per hash.
+ *   depth[h] = number of reads pushed so far whose bottom-s sketch holds reference hash h
+ * -- truncation to s first, as for covered; a read's sketch holds a hash once, so a read counts once per hash; repeats of a read count
+ * again (depth, unlike breadth, grows with them).  One uint32_t per distinct hash of the reference, at the indices of the seen set's bits
+ * (per slot of the key table, plus the two lifted hashes); it SATURATES at 2^32 - 1 and stays there.
+ * skx_stream_enable_depth has the preconditions and errors of skx_stream_enable_coverage (before the first read or after a reset:
+ * SKX_ERR_INVALID otherwise; no rare-hash index: SKX_ERR_UNSUPPORTED, stream untouched; second call: SKX_OK) and enables coverage too when
+ * it is not on yet.  Every scoring pass then also counts its (read, hash) pairs per hash and adds them, clamped, to the counters.  Rows,
+ * table and coverage are what they were.  skx_stream_reset zeroes the counters and keeps depth enabled; skx_stream_table_add and
+ * skx_stream_allreduce do not touch them; skx_stream_destroy frees them.  A stream that never enables depth allocates and launches nothing.
+ * The queries flush and count then, as the coverage queries do; indices, order, n == 0 and the error for an index out of range are those of
+ * skx_stream_coverage / _rows.  Each output may be NULL:
+ *   covered[g] = hashes of genome g's column with depth > 0: identical to skx_stream_coverage
+ *   total[g]   = sum of the stored (clamped) counters over g's hashes: equal to skx_stream_table's entry as long as nothing saturated and
+ *                neither skx_stream_table_add nor skx_stream_depth_import was used
+ *   median[g]  = LOWER median of the counters of g's covered hashes: the element at index (covered - 1) / 2 of their ascending order, 0
+ *                when covered == 0.  Integer and exact.  (Mash averages the two middle values of an even count; this library does not.)
+ * The first query allocates a scratch of at most 256 MiB (one uint32_t per hash of the genomes of one launch); the table is walked in
+ * chunks of as many 64-genome groups as fit.
+ * Portable state.  The key table is filled by atomic insertion: its slot layout differs between two builds of one reference, so the
+ * counters travel as (hash, count):
+ *   skx_stream_depth_count   *n = distinct reference hashes with depth > 0, lifted ones included
+ *   skx_stream_depth_export  those entries, order unspecified; *n is their number (not capped), hashes / counts [cap] take the first
+ *                            min(*n, cap)
+ *   skx_stream_depth_import  adds counts[i], clamped, to the counter of hashes[i] and marks the hash seen when counts[i] > 0; entries
+ *                            naming one hash twice add up; an entry whose hash is no hash of this reference is skipped and counted in
+ *                            *n_unknown (may be NULL).  Allowed at any time on a stream with depth: on a fresh stream it resumes a
+ *                            checkpoint, on top of reads it merges another rank's shard.  The running table is not touched (use
+ *                            skx_stream_table_add for the sums); after an import total[g] and the table differ.
+ * SKX_ERR_INVALID: a stream that never enabled depth; a NULL stream, list or count pointer.
+ */
+int skx_stream_enable_depth(skx_stream *st);
+int skx_stream_depth(skx_stream *st, uint32_t *covered, uint32_t *median, uint64_t *total);
+int skx_stream_depth_rows(skx_stream *st, const uint32_t *genomes, uint32_t n, uint32_t *covered, uint32_t *median, uint64_t *total);
+int skx_stream_depth_count(skx_stream *st, uint64_t *n);
+int skx_stream_depth_export(skx_stream *st, uint64_t *hashes, uint32_t *counts, uint64_t cap, uint64_t *n);
+int skx_stream_depth_import(skx_stream *st, const uint64_t *hashes, const uint32_t *counts, uint64_t n, uint64_t *n_unknown);
 void skx_stream_destroy(skx_stream *st);
 
 /*

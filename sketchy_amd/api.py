@@ -486,6 +486,52 @@ class SumOfSharedHashes:
         _lib.check(_lib.load().skx_stream_coverage_rank(self._h, top, _p(idx), _p(cov)))
         return idx, cov
 
+    def enable_depth(self):
+        """Give the stream one saturating counter per reference hash (skx_stream_enable_depth; enables coverage too): before the first
+        read, or after reset()."""
+        _lib.check(_lib.load().skx_stream_enable_depth(self._h))
+
+    def depth(self):
+        """(covered, median, total), each [n_genomes]: hashes of genome g's column seen at all (uint32), the lower median of how many reads
+        shared each of those (uint32), and the sum of the counters (uint64)."""
+        n = self.ref.n_genomes
+        cov, med, tot = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        _lib.check(_lib.load().skx_stream_depth(self._h, _p(cov), _p(med), _p(tot)))
+        return cov, med, tot
+
+    def depth_rows(self, genomes):
+        """The same for a list of global genome indices (any order, repeats allowed)."""
+        genomes = np.ascontiguousarray(genomes, np.uint32).reshape(-1)
+        n = len(genomes)
+        cov, med, tot = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.uint64)
+        _lib.check(_lib.load().skx_stream_depth_rows(self._h, _p(genomes), n, _p(cov), _p(med), _p(tot)))
+        return cov, med, tot
+
+    def depth_count(self) -> int:
+        """Distinct reference hashes seen so far (lifted ones included)."""
+        n = C.c_uint64(0)
+        _lib.check(_lib.load().skx_stream_depth_count(self._h, C.byref(n)))
+        return int(n.value)
+
+    def depth_export(self):
+        """The counters as (hashes uint64, counts uint32) of the hashes seen, in no particular order: the portable form of the state."""
+        cap = self.depth_count()
+        hashes, counts = np.zeros(cap, np.uint64), np.zeros(cap, np.uint32)
+        n = C.c_uint64(0)
+        _lib.check(_lib.load().skx_stream_depth_export(self._h, _p(hashes), _p(counts), cap, C.byref(n)))
+        assert int(n.value) == cap, "the stream moved between depth_count and depth_export"
+        return hashes, counts
+
+    def depth_import(self, hashes, counts) -> int:
+        """Add (hash, count) pairs to the counters (saturating; the hashes become seen); returns how many named no hash of this reference."""
+        hashes = np.ascontiguousarray(hashes, np.uint64).reshape(-1)
+        counts = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if len(hashes) != len(counts):
+            raise ValueError("hashes and counts differ in length")
+        unknown = C.c_uint64(0)
+        _lib.check(_lib.load().skx_stream_depth_import(self._h, _p(hashes), _p(counts), len(hashes), C.byref(unknown)))
+        return int(unknown.value)
+
     def consensus(self, top=None) -> np.ndarray:
         """Consensus codes of the CURRENT table: rank(top) followed by the reference's consensus_rows -> [F] / [n_species, F]."""
         idx, _ = self.rank(top)

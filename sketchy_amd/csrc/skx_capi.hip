@@ -1270,6 +1270,15 @@ struct skx_stream {
     u32 *d_cov_pad = nullptr, *d_cov_out = nullptr, *d_cov_list = nullptr, *d_cov_ridx = nullptr;
     u64 *d_cov_wide = nullptr, *d_cov_rsum = nullptr;
     u32 cov_list_cap = 0, cov_rank_cap = 0;
+    // depth of the stream (skx_stream_enable_depth; all NULL until then): d_depth = one saturating u32 per bit of d_seen, same indices; d_dep_tmp
+    // [dep_tmp_n = max(pcap, qcap_max)] = a pass's pairs per position in Q (zero between passes); d_dep_pad = the queries' per-genome results in padded order, one
+    // allocation {covered, max, median [n_pad] u32, total [n_pad] u64}; d_dep_list = {outputs total u64, covered, median, requested genomes,
+    // their groups} [dep_list_cap]; d_dep_vals = the select's scratch (first query; dep_vals_groups groups of 64 genomes per launch);
+    // d_dep_n = two counters of export / import
+    u32 *d_depth = nullptr, *d_dep_tmp = nullptr, *d_dep_pad = nullptr, *d_dep_vals = nullptr;
+    u64* d_dep_list = nullptr;
+    unsigned long long* d_dep_n = nullptr;
+    u32 dep_list_cap = 0, dep_vals_groups = 0, dep_tmp_n = 0;
     u32* h_poff = nullptr;   // pinned
     u64* h_offsets = nullptr;  // pinned
     // |Q| / pairs of the most recent pass whose dictionary has finished: the host only knows the pair count of a
@@ -1375,7 +1384,8 @@ static void stream_free(skx_stream* st) {
         if (st->own_lane_stream && st->lane[i].s) (void)hipStreamDestroy(st->lane[i].s);
     for (void* p : ptrs) (void)hipFree(p);
     for (void* p : {(void*)st->d_seen, (void*)st->d_cov_pad, (void*)st->d_cov_out, (void*)st->d_cov_list, (void*)st->d_cov_ridx,
-                    (void*)st->d_cov_wide, (void*)st->d_cov_rsum}) (void)hipFree(p);
+                    (void*)st->d_cov_wide, (void*)st->d_cov_rsum, (void*)st->d_depth, (void*)st->d_dep_tmp, (void*)st->d_dep_pad,
+                    (void*)st->d_dep_vals, (void*)st->d_dep_list, (void*)st->d_dep_n}) (void)hipFree(p);
     if (st->h_poff) (void)hipHostFree(st->h_poff);
     if (st->h_offsets) (void)hipHostFree(st->h_offsets);
     if (st->h_nq) (void)hipHostFree(st->h_nq);
@@ -2257,6 +2267,10 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
         HIPCHK(hipMemsetAsync(d_grp_any, 0, (size_t)n_grp_all * 4, hs));  // raised by the transpose
         if (P > 0) {
             skx::launch_pair_q(hs, st->d_pair_h[b], P, d_q, d_nq, d_pair_q, split_dict ? st->d_qrow : nullptr, st->d_bbase, st->d_btot, ref->max_ref);
+            // (a stream with depth enabled: every (read, hash) pair of the pass counts once for its hash -- while the pair hashes are still here)
+            if (st->d_depth && split_dict)
+                skx::launch_depth_mark(hs, st->d_pair_h[b], P, d_q, d_nq, q_bound, st->d_qinfo, st->d_bbase, st->d_btot, ref->max_ref, st->d_dep_tmp,
+                                       st->d_depth, ref->kt_mask + 1u);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(st->ev_pairq[b], hs));  // the set's hash set and pair hashes may be refilled
@@ -4204,6 +4218,10 @@ SKX_API int skx_stream_reset(skx_stream* st) {
     HIPCHK(hipStreamSynchronize(st->hs));
     HIPCHK(hipMemsetAsync(st->d_cum, 0, (size_t)st->ref->n_pad * 8, st->hs2));
     if (st->d_seen) HIPCHK(hipMemsetAsync(st->d_seen, 0, (size_t)st->seen_words * 4, st->hs2));  // (a new sample has seen nothing; coverage stays enabled)
+    if (st->d_depth) {  // (... and counted nothing; depth stays enabled)
+        HIPCHK(hipMemsetAsync(st->d_depth, 0, ((size_t)st->ref->kt_mask + 3u) * 4, st->hs2));
+        HIPCHK(hipMemsetAsync(st->d_dep_tmp, 0, (size_t)st->dep_tmp_n * 4, st->hs2));
+    }
     HIPCHK(hipStreamSynchronize(st->hs2));
     st->reads_total = 0;
     st->h_nq[2] = 1; st->h_nq[3] = 1;  // (a new sample: every genome is a candidate again)
@@ -4388,6 +4406,207 @@ SKX_API int skx_stream_coverage_rank(skx_stream* st, uint32_t top_k, uint32_t* i
     HIPCHK(hipMemcpyAsync(sum.data(), st->d_cov_rsum, rows * 8, hipMemcpyDeviceToHost, st->hs));
     HIPCHK(hipStreamSynchronize(st->hs));
     for (size_t i = 0; i < rows; ++i) covered[i] = (u32)sum[i];
+    return SKX_OK;
+}
+
+// ------------------------------------------------------------------ depth of a stream
+// depth[h] = reads pushed so far whose bottom-s sketch holds reference hash h: one saturating u32 beside every bit of the seen set.  The
+// counts of every pass run on the scan stream (run_pass_multi, behind the pass's pair_q); the queries, export and import run there too.
+// The select's scratch holds every counter of the groups of one launch: it is bounded by kDepthScratch, the groups are walked in chunks.
+constexpr size_t kDepthScratch = (size_t)256 << 20;
+SKX_API int skx_stream_enable_depth(skx_stream* st) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (st->d_depth) return SKX_OK;
+    const skx_ref* ref = st->ref;
+    if (!ref->d_kt_key)
+        return fail(SKX_ERR_UNSUPPORTED, "skx_stream_enable_depth: the reference has no rare-hash index (policy rare_hash_genomes = 0): nothing gives a "
+                                         "query hash a persistent identity");
+    uint64_t reads = 0;
+    SKXCHK(skx_stream_reads(st, &reads));
+    if (reads) return fail(SKX_ERR_INVALID, "skx_stream_enable_depth: the stream has taken %llu reads already (enable it first, or after a reset)",
+                           (unsigned long long)reads);
+    SKXCHK(skx_stream_enable_coverage(st));  // (the bitmap stays the truth for `covered`; enabled already: nothing happens)
+    SKXCHK(use_device(st->device));
+    const size_t n_ctr = (size_t)ref->kt_mask + 3u;
+    u32 *depth = nullptr, *tmp = nullptr, *pad = nullptr;
+    unsigned long long* ctr = nullptr;
+    hipError_t e = hipMalloc(&depth, n_ctr * 4);
+    const u32 tmp_n = std::max(st->pcap, std::max(st->qcap, st->qcap_max));  // (positions in a pass's Q: below its q_bound <= qcap, which may grow to qcap_max)
+    if (e == hipSuccess) e = hipMalloc(&tmp, (size_t)tmp_n * 4);
+    if (e == hipSuccess) e = hipMalloc(&pad, (size_t)ref->n_pad * 20);
+    if (e == hipSuccess) e = hipMalloc(&ctr, 16);
+    if (e == hipSuccess) e = hipMemset(depth, 0, n_ctr * 4);
+    if (e == hipSuccess) e = hipMemset(tmp, 0, (size_t)tmp_n * 4);
+    if (e != hipSuccess) {  // (the counters are all or nothing; coverage, if this call enabled it, stays)
+        (void)hipFree(depth); (void)hipFree(tmp); (void)hipFree(pad); (void)hipFree(ctr);
+        (void)hipGetLastError();
+        return fail(SKX_ERR_HIP, "skx_stream_enable_depth: %s", hipGetErrorString(e));
+    }
+    st->d_dep_tmp = tmp; st->dep_tmp_n = tmp_n; st->d_dep_pad = pad; st->d_dep_n = ctr;
+    st->d_depth = depth;
+    return SKX_OK;
+}
+// {total u64, covered, median, genomes, groups u32} [dep_list_cap], one allocation grown to the longest list asked for
+static int depth_list_room(skx_stream* st, u32 n) {
+    if (n <= st->dep_list_cap) return SKX_OK;
+    HIPCHK(hipStreamSynchronize(st->hs));
+    (void)hipFree(st->d_dep_list);
+    st->d_dep_list = nullptr; st->dep_list_cap = 0;
+    const u32 cap = std::max<u32>(n, 64u);
+    HIPCHK(hipMalloc(&st->d_dep_list, (size_t)cap * 24));
+    st->dep_list_cap = cap;
+    return SKX_OK;
+}
+// walk and select on the scan stream, behind the counts of every pass queued so far (the caller has flushed): d_groups == NULL -> every
+// group of 64 padded genomes.  Leaves covered / max / median / total of the walked genomes in d_dep_pad.
+static int depth_walk(skx_stream* st, const u32* d_groups, u32 n_groups) {
+    const skx_ref* ref = st->ref;
+    const u32 n_pad = ref->n_pad;
+    if (!d_groups) n_groups = n_pad / 64u;
+    if (!st->d_dep_vals) {  // (first query: as many groups per launch as the budget holds, never more than the table has)
+        size_t budget = kDepthScratch;
+        if (const char* k = skx::knob("SKX_DEPTH_SCRATCH")) budget = (size_t)strtoull(k, nullptr, 10);  // experiment knob: bytes
+        const size_t per = skx::depth_vals_per_group(ref->s) * 4;
+        const u32 g = (u32)std::min<size_t>(std::max<size_t>(budget / per, 1), n_pad / 64u);
+        HIPCHK(hipMalloc(&st->d_dep_vals, per * g));
+        st->dep_vals_groups = g;
+    }
+    u64* d_tot = (u64*)st->d_dep_pad;
+    u32 *d_cov = st->d_dep_pad + 2 * (size_t)n_pad, *d_max = d_cov + n_pad, *d_med = d_max + n_pad;
+    HIPCHK(hipMemsetAsync(st->d_dep_pad, 0, (size_t)n_pad * 20, st->hs));
+    for (u32 g0 = 0; g0 < n_groups; g0 += st->dep_vals_groups) {  // (launches on one stream: a chunk's select is through before the next walk)
+        const u32 cnt = std::min(st->dep_vals_groups, n_groups - g0);
+        skx::launch_depth_walk(st->hs, ref->d_mat, ref->s, d_groups ? d_groups + g0 : nullptr, g0, cnt, ref->d_kt_key, ref->kt_mask, st->d_depth,
+                               ref->d_exc_g, ref->d_exc_h, ref->n_exc, d_cov, d_tot, d_max, d_med, st->d_dep_vals);
+    }
+    HIPCHK(hipGetLastError());
+    return SKX_OK;
+}
+// gather for n genomes (d_genomes == NULL: genomes 0 .. n - 1) and copy what the caller wants; waits for the stream
+static int depth_results(skx_stream* st, const u32* d_genomes, u32 n, uint32_t* covered, uint32_t* median, uint64_t* total) {
+    const skx_ref* ref = st->ref;
+    const u32 n_pad = ref->n_pad, cap = st->dep_list_cap;
+    const u64* d_tot = (const u64*)st->d_dep_pad;
+    const u32 *d_cov = st->d_dep_pad + 2 * (size_t)n_pad, *d_med = d_cov + 2 * (size_t)n_pad;
+    u64* o_tot = st->d_dep_list;
+    u32 *o_cov = (u32*)(st->d_dep_list + cap), *o_med = o_cov + cap;
+    skx::launch_depth_gather(st->hs, d_cov, d_med, d_tot, ref->d_real2pad, d_genomes, n, o_cov, o_med, o_tot);
+    HIPCHK(hipGetLastError());
+    if (covered) HIPCHK(hipMemcpyAsync(covered, o_cov, (size_t)n * 4, hipMemcpyDeviceToHost, st->hs));
+    if (median) HIPCHK(hipMemcpyAsync(median, o_med, (size_t)n * 4, hipMemcpyDeviceToHost, st->hs));
+    if (total) HIPCHK(hipMemcpyAsync(total, o_tot, (size_t)n * 8, hipMemcpyDeviceToHost, st->hs));
+    return SKX_OK;
+}
+SKX_API int skx_stream_depth(skx_stream* st, uint32_t* covered, uint32_t* median, uint64_t* total) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth: depth was never enabled on this stream");
+    SKXCHK(use_device(st->device));
+    const skx_ref* ref = st->ref;
+    SKXCHK(flush_pending(st));
+    SKXCHK(depth_list_room(st, ref->n_genomes));
+    int rc = depth_walk(st, nullptr, 0);
+    if (rc == SKX_OK) rc = depth_results(st, nullptr, ref->n_genomes, covered, median, total);
+    const hipError_t e = hipStreamSynchronize(st->hs);
+    if (rc == SKX_OK && e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_stream_depth: %s", hipGetErrorString(e));
+    return rc;
+}
+SKX_API int skx_stream_depth_rows(skx_stream* st, const uint32_t* genomes, uint32_t n, uint32_t* covered, uint32_t* median, uint64_t* total) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_rows: depth was never enabled on this stream");
+    if (n == 0) return SKX_OK;
+    if (!genomes) return fail(SKX_ERR_INVALID, "NULL argument");
+    const skx_ref* ref = st->ref;
+    for (u32 i = 0; i < n; ++i)
+        if (genomes[i] >= ref->n_genomes) return fail(SKX_ERR_INVALID, "skx_stream_depth_rows: genomes[%u] = %u outside 0..n_genomes - 1 = %u", i, genomes[i], ref->n_genomes - 1);
+    SKXCHK(use_device(st->device));
+    // the aligned 64-genome groups (padded order) that hold a requested genome, each once
+    std::vector<u32> grp(n);
+    for (u32 i = 0; i < n; ++i) {
+        u32 sp = 0;
+        while (sp + 1 < ref->n_species && genomes[i] >= ref->sp_real0[sp + 1]) ++sp;
+        grp[i] = (ref->sp_g0[sp] + (genomes[i] - ref->sp_real0[sp])) / 64u;
+    }
+    std::sort(grp.begin(), grp.end());
+    grp.erase(std::unique(grp.begin(), grp.end()), grp.end());
+    SKXCHK(flush_pending(st));
+    SKXCHK(depth_list_room(st, n));
+    u32 *d_gen = (u32*)(st->d_dep_list + st->dep_list_cap) + 2 * (size_t)st->dep_list_cap, *d_grp = d_gen + st->dep_list_cap;
+    HIPCHK(hipMemcpyAsync(d_gen, genomes, (size_t)n * 4, hipMemcpyHostToDevice, st->hs));
+    HIPCHK(hipMemcpyAsync(d_grp, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, st->hs));
+    int rc = depth_walk(st, d_grp, (u32)grp.size());
+    if (rc == SKX_OK) rc = depth_results(st, d_gen, n, covered, median, total);
+    const hipError_t e = hipStreamSynchronize(st->hs);  // (`genomes` and the group list are only borrowed until here, on every way out)
+    if (rc == SKX_OK && e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_stream_depth_rows: %s", hipGetErrorString(e));
+    return rc;
+}
+// ---- portable state: (hash, count), keyed by the hash because the key table's slot layout is not reproducible between two builds
+static int depth_export_run(skx_stream* st, uint64_t* hashes, uint32_t* counts, uint64_t cap, uint64_t* n) {
+    const skx_ref* ref = st->ref;
+    const u64 slots = (u64)ref->kt_mask + 1u;
+    SKXCHK(use_device(st->device));
+    SKXCHK(flush_pending(st));
+    unsigned long long have = 0;
+    HIPCHK(hipMemsetAsync(st->d_dep_n, 0, 16, st->hs));
+    skx::launch_depth_export(st->hs, ref->d_kt_key, st->d_depth, slots, nullptr, nullptr, 0, st->d_dep_n);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&have, st->d_dep_n, 8, hipMemcpyDeviceToHost, st->hs));
+    HIPCHK(hipStreamSynchronize(st->hs));
+    *n = have;
+    const u64 take = std::min<u64>(have, hashes ? cap : 0);
+    if (take == 0) return SKX_OK;
+    u64* d_h = nullptr;  // (a call's own buffers: hashes u64 [take], counts u32 [take])
+    HIPCHK(hipMalloc(&d_h, (size_t)take * 12));
+    u32* d_c = (u32*)(d_h + take);
+    int rc = SKX_OK;
+    hipError_t e = hipMemsetAsync(st->d_dep_n + 1, 0, 8, st->hs);
+    if (e == hipSuccess) {
+        skx::launch_depth_export(st->hs, ref->d_kt_key, st->d_depth, slots, d_h, d_c, take, st->d_dep_n + 1);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(hashes, d_h, (size_t)take * 8, hipMemcpyDeviceToHost, st->hs);
+    if (e == hipSuccess) e = hipMemcpyAsync(counts, d_c, (size_t)take * 4, hipMemcpyDeviceToHost, st->hs);
+    const hipError_t e2 = hipStreamSynchronize(st->hs);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_stream_depth_export: %s", hipGetErrorString(e));
+    (void)hipFree(d_h);
+    return rc;
+}
+SKX_API int skx_stream_depth_count(skx_stream* st, uint64_t* n) {
+    if (!st || !n) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_count: depth was never enabled on this stream");
+    return depth_export_run(st, nullptr, nullptr, 0, n);
+}
+SKX_API int skx_stream_depth_export(skx_stream* st, uint64_t* hashes, uint32_t* counts, uint64_t cap, uint64_t* n) {
+    if (!st || !n || (cap && (!hashes || !counts))) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_export: depth was never enabled on this stream");
+    return depth_export_run(st, cap ? hashes : nullptr, counts, cap, n);
+}
+SKX_API int skx_stream_depth_import(skx_stream* st, const uint64_t* hashes, const uint32_t* counts, uint64_t n, uint64_t* n_unknown) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_import: depth was never enabled on this stream");
+    if (n_unknown) *n_unknown = 0;
+    if (n == 0) return SKX_OK;
+    if (!hashes || !counts) return fail(SKX_ERR_INVALID, "NULL argument");
+    const skx_ref* ref = st->ref;
+    SKXCHK(use_device(st->device));
+    SKXCHK(flush_pending(st));
+    u64* d_h = nullptr;
+    HIPCHK(hipMalloc(&d_h, (size_t)n * 12));
+    u32* d_c = (u32*)(d_h + n);
+    unsigned long long unknown = 0;
+    hipError_t e = hipMemcpyAsync(d_h, hashes, (size_t)n * 8, hipMemcpyHostToDevice, st->hs);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_c, counts, (size_t)n * 4, hipMemcpyHostToDevice, st->hs);
+    if (e == hipSuccess) e = hipMemsetAsync(st->d_dep_n, 0, 8, st->hs);
+    if (e == hipSuccess) {
+        skx::launch_depth_import(st->hs, d_h, d_c, n, ref->d_kt_key, ref->kt_mask, st->d_depth, st->d_seen, st->d_dep_n);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&unknown, st->d_dep_n, 8, hipMemcpyDeviceToHost, st->hs);
+    const hipError_t e2 = hipStreamSynchronize(st->hs);  // (the caller's arrays and the staging buffer are only borrowed until here)
+    if (e == hipSuccess) e = e2;
+    (void)hipFree(d_h);
+    if (e != hipSuccess) return fail(SKX_ERR_HIP, "skx_stream_depth_import: %s", hipGetErrorString(e));
+    if (n_unknown) *n_unknown = unknown;
     return SKX_OK;
 }
 

@@ -4454,6 +4454,240 @@ __global__ void coverage_widen_kernel(const u32* __restrict__ covered, u32 n_pad
 }
 
 // =====================================================================================
+// depth of a stream: how OFTEN has a reference hash been shared (skx_stream_enable_depth)
+// =====================================================================================
+// The state is one u32 per bit of the seen set, same indices: depth[slot] = reads so far whose bottom-s sketch holds key[slot], saturating
+// at 2^32 - 1.  A read's sketch holds a hash once, so a pass adds, per distinct hash, the number of its (read, hash) pairs that carry it.
+// Two kernels behind the pass's pair_q_kernel (the pair hashes and the bucket bases are still this pass's):
+//   depth_count_kernel  one lane per pair: its position in Q as pair_q_kernel finds it, atomicAdd into tmp[position] -- lanes of a wave
+//                       with the same position add once (a hash every read holds is one address for all pairs of the pass)
+//   depth_apply_kernel  one lane per distinct hash: depth[slot] = sat(depth[slot] + tmp[i]), slot from qinfo as seen_mark_kernel; tmp[i]
+//                       goes back to zero (it is zero between passes).  No atomics: a slot occurs once in Q, passes are ordered on the
+//                       scan stream -- and a bare atomicAdd on the counters could not saturate.
+__device__ __forceinline__ u32 sat_add_u32(u32 a, u32 b) { const u32 t = a + b; return t < a ? 0xFFFFFFFFu : t; }
+__global__ __launch_bounds__(256) void depth_count_kernel(const u64* __restrict__ pair_h, u32 n_pairs, const u64* __restrict__ q,
+                                                          const u32* __restrict__ n_q, u32 q_bound, const u32* __restrict__ bbase,
+                                                          const u32* __restrict__ btot, u32 bshift, u32* __restrict__ tmp) {
+    const u32 p = blockIdx.x * 256u + threadIdx.x, nq = min(*n_q, q_bound);
+    u32 pos = 0xFFFFFFFFu;
+    if (p < n_pairs) {
+        const u64 h = pair_h[p];
+        const u32 b = dict_bucket(h, bshift);
+        u32 at = btot[b >> 10] + bbase[b];
+        while (at < nq && q[at] < h) ++at;
+        if (at < nq && q[at] == h) pos = at;  // (every pair's hash is in Q; a dictionary cut at q_bound loses the pass anyway)
+    }
+    // lanes with the same position: the lowest of them adds their number
+    u64 todo = __ballot(pos != 0xFFFFFFFFu);
+    const u64 me = 1ull << (threadIdx.x & 63u);
+    while (todo) {
+        const u32 first = __shfl(pos, __ffsll((long long)todo) - 1);
+        const u64 same = __ballot(pos == first) & todo;
+        if ((same & (0ull - same)) == me) atomicAdd(&tmp[first], (u32)__popcll(same));
+        todo &= ~same;
+    }
+}
+__global__ __launch_bounds__(256) void depth_apply_kernel(const u64* __restrict__ q, const u32* __restrict__ n_q, u32 q_bound,
+                                                          const u32* __restrict__ qinfo, u32* __restrict__ tmp, u32* __restrict__ depth,
+                                                          u32 kt_slots) {
+    const u32 nq = min(*n_q, q_bound), i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= nq) return;
+    const u32 c = tmp[i];
+    if (!c) return;
+    tmp[i] = 0;
+    const u64 h = q[i];
+    u32 at;
+    if (h >= kEmpty) at = kt_slots + (u32)(h - kEmpty);
+    else {
+        at = qinfo[i];
+        if (at == kSlotNone || at >= kt_slots) return;
+    }
+    depth[at] = sat_add_u32(depth[at], c);
+}
+// The query side, part 1: coverage_walk_kernel's walk (same unit, same lanes, four dependent probes in flight, the lifted hashes from
+// exc_g / exc_h in the block of rank chunk 0), reading the counter where that reads the bit.  The probes are the expensive part and happen
+// once: per padded genome the walk adds up covered (counters > 0) and total, keeps the maximum, and leaves every counter of the group in
+// vals[group of the launch][s + 2][64] (rank-major, lanes along the genomes: 256-byte stores; rows s and s + 1: the lifted hashes; zero where
+// the matrix holds padding or the hash was never seen) for the select below.  covered / total / vmax [n_pad]: zero on entry.
+__global__ __launch_bounds__(256) void depth_walk_kernel(const u64* __restrict__ mat, u32 s, const u32* __restrict__ groups, u32 g0,
+                                                         const u64* __restrict__ key, u32 mask, const u32* __restrict__ depth,
+                                                         const u32* __restrict__ exc_g, const u64* __restrict__ exc_h, u32 n_exc,
+                                                         u32* __restrict__ covered, u64* __restrict__ total, u32* __restrict__ vmax,
+                                                         u32* __restrict__ vals) {
+    __shared__ u32 part_n[4][64], part_m[4][64];
+    __shared__ u64 part_t[4][64];
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u32 p = (groups ? groups[blockIdx.x] : g0 + blockIdx.x) * 64u + lane;  // (64 | 256: the group lies inside one tile)
+    const u64* col = mat + (size_t)(p / kTileGenomes) * s * kTileGenomes + p % kTileGenomes;
+    u32* out = vals + (size_t)blockIdx.x * (s + 2u) * 64u + lane;
+    const u32 r0 = blockIdx.y * kCovRanks, r1 = min(s, r0 + kCovRanks);
+    u32 n = 0, mx = 0;
+    u64 tot = 0;
+    for (u32 r = r0 + wv; r < r1; r += 16u) {
+        u64 h[4];
+        u32 slot[4];
+#pragma unroll
+        for (u32 j = 0; j < 4u; ++j) {
+            const u32 rr = r + 4u * j;
+            h[j] = rr < r1 ? col[(size_t)rr * kTileGenomes] : kPad;
+        }
+#pragma unroll
+        for (u32 j = 0; j < 4u; ++j) slot[j] = kt_start(h[j], mask);
+#pragma unroll
+        for (u32 j = 0; j < 4u; ++j) {
+            const u32 rr = r + 4u * j;
+            if (rr >= r1) continue;
+            u32 v = 0;
+            if (h[j] < kEmpty) {
+                u32 sl = slot[j], tries = 0;
+                for (;;) {
+                    const u64 kk = key[sl];
+                    if (kk == h[j]) { v = depth[sl]; break; }
+                    if (kk == kPad || ++tries > mask) break;  // (cannot happen: every stored hash is a key)
+                    sl = (sl + 1u) & mask;
+                }
+            }
+            out[(size_t)rr * 64u] = v;
+            n += v != 0; tot += v; mx = max(mx, v);
+        }
+    }
+    if (blockIdx.y == 0 && wv == 0) {
+        u32 lv[2] = {0u, 0u};
+        if (n_exc) {
+            u32 a = 0, b = n_exc;  // first exception of a genome >= p
+            while (a < b) {
+                const u32 mid = (a + b) >> 1;
+                if (exc_g[mid] < p) a = mid + 1; else b = mid;
+            }
+            for (; a < n_exc && exc_g[a] == p; ++a) {
+                const u32 w = (u32)(exc_h[a] - kEmpty) & 1u;
+                lv[w] = depth[(size_t)mask + 1u + w];
+            }
+        }
+        out[(size_t)s * 64u] = lv[0];
+        out[(size_t)(s + 1u) * 64u] = lv[1];
+        n += (lv[0] != 0) + (lv[1] != 0); tot += (u64)lv[0] + lv[1]; mx = max(mx, max(lv[0], lv[1]));
+    }
+    part_n[wv][lane] = n; part_m[wv][lane] = mx; part_t[wv][lane] = tot;
+    __syncthreads();
+    if (wv == 0) {
+        const u32 tn = part_n[0][lane] + part_n[1][lane] + part_n[2][lane] + part_n[3][lane];
+        if (tn) {
+            atomicAdd(&covered[p], tn);
+            atomicAdd(&total[p], part_t[0][lane] + part_t[1][lane] + part_t[2][lane] + part_t[3][lane]);
+            atomicMax(&vmax[p], max(max(part_m[0][lane], part_m[1][lane]), max(part_m[2][lane], part_m[3][lane])));
+        }
+    }
+}
+// Part 2: the lower median of a genome's covered counters = the element of rank (covered - 1) / 2 of the non-zero values of its column of
+// vals, ascending.  One workgroup per group of the launch, an MSB-first radix select: per byte round the four waves read the group's rows
+// (lane = genome: 256 contiguous bytes per row) and count, for every genome, the values that agree with its prefix so far by their next byte
+// in hist[256 bins][64 genomes] (LDS, 64 KiB of the CU's 160: two workgroups per CU; the genome on the bank, so the lanes of a wave never
+// conflict whatever their bins; the four waves meet on a word, hence ds atomics without return); wave 0 then walks the 256 bins of its lane's
+// genome to the bin that holds the rank.  Only the byte rounds the group's largest counter needs: one for a stream no deeper than 255.
+__global__ __launch_bounds__(256) void depth_select_kernel(const u32* __restrict__ vals, u32 s, const u32* __restrict__ groups, u32 g0,
+                                                           const u32* __restrict__ covered, const u32* __restrict__ vmax,
+                                                           u32* __restrict__ median) {
+    __shared__ u32 hist[256][64];
+    __shared__ u32 pre[64], want[64];
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u32 p = (groups ? groups[blockIdx.x] : g0 + blockIdx.x) * 64u + lane;
+    const u32* col = vals + (size_t)blockIdx.x * (s + 2u) * 64u + lane;
+    const u32 cov = covered[p];
+    u32 gmax = vmax[p];
+#pragma unroll
+    for (u32 d = 32u; d; d >>= 1) gmax = max(gmax, (u32)__shfl_xor((int)gmax, (int)d));
+    if (gmax == 0) { if (wv == 0) median[p] = 0; return; }  // (uniform over the block: nothing of the group was seen)
+    if (wv == 0) { pre[lane] = 0; want[lane] = cov ? (cov - 1u) / 2u : 0u; }
+    const int top = gmax >> 24 ? 3 : gmax >> 16 ? 2 : gmax >> 8 ? 1 : 0;
+    for (int b = top; b >= 0; --b) {
+        for (u32 i = threadIdx.x; i < 256u * 64u; i += 256u) (&hist[0][0])[i] = 0;
+        __syncthreads();
+        const u32 mine = pre[lane], sh = 8u * (u32)b;
+        for (u32 r = wv; r < s + 2u; r += 4u) {
+            const u32 v = col[(size_t)r * 64u];
+            if (v && (u32)((u64)v >> (sh + 8u)) == mine) atomicAdd(&hist[(v >> sh) & 255u][lane], 1u);
+        }
+        __syncthreads();
+        if (wv == 0 && cov) {
+            u32 k = want[lane], bin = 0;
+            for (; bin < 255u; ++bin) {
+                const u32 c = hist[bin][lane];
+                if (k < c) break;
+                k -= c;
+            }
+            want[lane] = k; pre[lane] = (mine << 8) | bin;
+        }
+        __syncthreads();
+    }
+    if (wv == 0) median[p] = cov ? pre[lane] : 0u;
+}
+// out[i] of the three results for padded genome real2pad[genomes ? genomes[i] : i]; an output that is NULL is not wanted
+__global__ void depth_gather_kernel(const u32* __restrict__ covered, const u32* __restrict__ median, const u64* __restrict__ total,
+                                    const u32* __restrict__ real2pad, const u32* __restrict__ genomes, u32 n, u32* __restrict__ out_cov,
+                                    u32* __restrict__ out_med, u64* __restrict__ out_tot) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const u32 p = real2pad[genomes ? genomes[i] : i];
+    out_cov[i] = covered[p]; out_med[i] = median[p]; out_tot[i] = total[p];
+}
+// Portable state: the counters by HASH (the key table is filled by atomic insertion: its slot layout differs between two builds of one
+// reference).  depth_export_kernel: every index with a counter > 0 -> (key[slot] or the lifted value, counter) at the next free place;
+// *n counts them all, the arrays take the first cap (hashes == NULL: count only).
+__global__ __launch_bounds__(256) void depth_export_kernel(const u64* __restrict__ key, const u32* __restrict__ depth, u64 kt_slots,
+                                                           u64* __restrict__ hashes, u32* __restrict__ counts, u64 cap,
+                                                           unsigned long long* __restrict__ n) {
+    for (u64 i0 = (u64)blockIdx.x * 256u; i0 < kt_slots + 2u; i0 += (u64)gridDim.x * 256u) {
+        const u64 i = i0 + threadIdx.x;
+        const u32 c = i < kt_slots + 2u ? depth[i] : 0u;
+        const u64 live = __ballot(c != 0);
+        if (!live) continue;
+        const u32 lane = threadIdx.x & 63u;
+        unsigned long long base = 0;
+        if (lane == (u32)__ffsll((long long)live) - 1u) base = atomicAdd(n, (unsigned long long)__popcll(live));
+        base = __shfl(base, __ffsll((long long)live) - 1);
+        if (c && hashes) {
+            const u64 at = base + (u64)__popcll(live & ((1ull << lane) - 1ull));
+            if (at < cap) { hashes[at] = i < kt_slots ? key[i] : kEmpty + (i - kt_slots); counts[at] = c; }
+        }
+    }
+}
+// depth_import_kernel: one lane per entry.  A hash >= kEmpty is a lifted one; any other is looked up in the key table (classify_a_kernel's
+// probe) and skipped and counted in *n_unknown when it is no key of this reference.  Entries of one list may name a hash twice and must add
+// up: the add is a compare-and-swap loop around the clamp.  A non-zero count also sets the hash's bit of the seen set.
+__global__ __launch_bounds__(256) void depth_import_kernel(const u64* __restrict__ hashes, const u32* __restrict__ counts, u64 n,
+                                                           const u64* __restrict__ key, u32 mask, u32* __restrict__ depth,
+                                                           u32* __restrict__ seen, unsigned long long* __restrict__ n_unknown) {
+    const u64 i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const u64 h = hashes[i];
+    const u32 c = counts[i];
+    u64 at;
+    if (h >= kEmpty) at = (u64)mask + 1u + (h - kEmpty);
+    else {
+        u32 sl = kt_start(h, mask), tries = 0;
+        for (;;) {
+            const u64 kk = key[sl];
+            if (kk == h) break;
+            if (kk == kPad || ++tries > mask) { atomicAdd(n_unknown, 1ull); return; }
+            sl = (sl + 1u) & mask;
+        }
+        at = sl;
+    }
+    if (!c) return;
+    u32 old = depth[at];
+    for (;;) {
+        const u32 nv = sat_add_u32(old, c);
+        if (nv == old) break;  // (saturated already)
+        const u32 was = atomicCAS(&depth[at], old, nv);
+        if (was == old) break;
+        old = was;
+    }
+    const u32 m = 1u << (u32)(at & 31u);
+    if (!(seen[at >> 5] & m)) atomicOr(&seen[at >> 5], m);
+}
+
+// =====================================================================================
 // the table without the ranking, and the genomes a batch's ranking has to look at (round 5)
 // =====================================================================================
 // Rounds 1-4 took the running table out of the ranking chain: per-segment increments, chunk sums, prefixes -- every pair's 64-byte
@@ -6240,6 +6474,38 @@ void launch_coverage_gather(hipStream_t st, const u32* covered, const u32* real2
 }
 void launch_coverage_widen(hipStream_t st, const u32* covered, u32 n_pad, u64* wide) {
     hipLaunchKernelGGL(coverage_widen_kernel, dim3(cdiv(n_pad, 256)), dim3(256), 0, st, covered, n_pad, wide);
+}
+void launch_depth_mark(hipStream_t st, const u64* pair_h, u32 n_pairs, const u64* q, const u32* n_q, u32 q_bound, const u32* qinfo,
+                       const u32* bbase, const u32* btot, u64 max_ref, u32* tmp, u32* depth, u32 kt_slots) {
+    if (n_pairs == 0 || q_bound == 0) return;
+    hipLaunchKernelGGL(depth_count_kernel, dim3(cdiv(n_pairs, 256)), dim3(256), 0, st, pair_h, n_pairs, q, n_q, q_bound, bbase, btot,
+                       dict_bshift(max_ref), tmp);
+    hipLaunchKernelGGL(depth_apply_kernel, dim3(cdiv(q_bound, 256)), dim3(256), 0, st, q, n_q, q_bound, qinfo, tmp, depth, kt_slots);
+}
+void launch_depth_walk(hipStream_t st, const u64* mat, u32 s, const u32* groups, u32 g0, u32 n_groups, const u64* key, u32 mask,
+                       const u32* depth, const u32* exc_g, const u64* exc_h, u32 n_exc, u32* covered, u64* total, u32* vmax, u32* median,
+                       u32* vals) {
+    if (n_groups == 0 || s == 0) return;
+    hipLaunchKernelGGL(depth_walk_kernel, dim3(n_groups, cdiv(s, kCovRanks)), dim3(256), 0, st, mat, s, groups, g0, key, mask, depth, exc_g,
+                       exc_h, n_exc, covered, total, vmax, vals);
+    hipLaunchKernelGGL(depth_select_kernel, dim3(n_groups), dim3(256), 0, st, vals, s, groups, g0, covered, vmax, median);
+}
+void launch_depth_gather(hipStream_t st, const u32* covered, const u32* median, const u64* total, const u32* real2pad, const u32* genomes,
+                         u32 n, u32* out_cov, u32* out_med, u64* out_tot) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(depth_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, covered, median, total, real2pad, genomes, n, out_cov,
+                       out_med, out_tot);
+}
+void launch_depth_export(hipStream_t st, const u64* key, const u32* depth, u64 kt_slots, u64* hashes, u32* counts, u64 cap,
+                         unsigned long long* n) {
+    const u32 nb = (u32)std::min<u64>((kt_slots + 2u + 255u) / 256u, 4096u);
+    hipLaunchKernelGGL(depth_export_kernel, dim3(nb), dim3(256), 0, st, key, depth, kt_slots, hashes, counts, cap, n);
+}
+void launch_depth_import(hipStream_t st, const u64* hashes, const u32* counts, u64 n, const u64* key, u32 mask, u32* depth, u32* seen,
+                         unsigned long long* n_unknown) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(depth_import_kernel, dim3((u32)((n + 255u) / 256u)), dim3(256), 0, st, hashes, counts, n, key, mask, depth, seen,
+                       n_unknown);
 }
 
 // =====================================================================================

@@ -407,6 +407,26 @@ void launch_coverage_walk(hipStream_t st, const u64* mat, u32 s, const u32* grou
 // out[i] = covered[real2pad[genomes ? genomes[i] : i]], i < n;  wide[p] = covered[p], p < n_pad (for launch_rank_table)
 void launch_coverage_gather(hipStream_t st, const u32* covered, const u32* real2pad, const u32* genomes, u32 n, u32* out);
 void launch_coverage_widen(hipStream_t st, const u32* covered, u32 n_pad, u64* wide);
+// ---- depth of a stream (skx_kernels.hip, "depth of a stream").  depth: one u32 per bit of `seen`, same indices, saturating.
+// launch_depth_mark: behind launch_pair_q of the same pass, same stream (pair_h, q, n_q, bbase, btot: its; qinfo: its launch_classify's);
+// tmp [>= q_bound] is zero on entry and zero again afterwards.
+void launch_depth_mark(hipStream_t st, const u64* pair_h, u32 n_pairs, const u64* q, const u32* n_q, u32 q_bound, const u32* qinfo,
+                       const u32* bbase, const u32* btot, u64 max_ref, u32* tmp, u32* depth, u32 kt_slots);
+// per padded genome of the groups groups[0 .. n_groups) (NULL: groups g0 .. g0 + n_groups - 1): covered += counters > 0, total += their sum,
+// vmax = their maximum (all three zero on entry), median = the lower median of the counters > 0; vals: scratch of depth_vals_per_group(s)
+// u32 per group of the launch
+inline size_t depth_vals_per_group(u32 s) { return ((size_t)s + 2u) * 64u; }
+void launch_depth_walk(hipStream_t st, const u64* mat, u32 s, const u32* groups, u32 g0, u32 n_groups, const u64* key, u32 mask,
+                       const u32* depth, const u32* exc_g, const u64* exc_h, u32 n_exc, u32* covered, u64* total, u32* vmax, u32* median,
+                       u32* vals);
+void launch_depth_gather(hipStream_t st, const u32* covered, const u32* median, const u64* total, const u32* real2pad, const u32* genomes,
+                         u32 n, u32* out_cov, u32* out_med, u64* out_tot);
+// *n += indices with a counter > 0 (zero on entry); hashes / counts [cap] take the first cap of them (hashes == NULL: count only)
+void launch_depth_export(hipStream_t st, const u64* key, const u32* depth, u64 kt_slots, u64* hashes, u32* counts, u64 cap,
+                         unsigned long long* n);
+// depth[hash's index] = sat(+ counts[i]), its seen bit set where counts[i] > 0; *n_unknown += entries that are no key (zero on entry)
+void launch_depth_import(hipStream_t st, const u64* hashes, const u32* counts, u64 n, const u64* key, u32 mask, u32* depth, u32* seen,
+                         unsigned long long* n_unknown);
 
 // ---- pooled sketches (skx_kernels.hip, "pooled sketches"): the bottom-s distinct hashes of the union of a group's rows
 // One round of the segmented merge tree: items[i] = {left row, partner row or 0xFFFFFFFF (no partner: the row is copied)}; rows are

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -81,6 +82,10 @@ extern "C" int skx_call_rows(int device, const uint32_t* idx, const uint64_t* su
 extern "C" int skx_stream_enable_coverage(skx_stream* st) __attribute__((weak));
 extern "C" int skx_stream_coverage(skx_stream* st, uint32_t* covered) __attribute__((weak));
 extern "C" int skx_stream_table(skx_stream* st, uint64_t* cum) __attribute__((weak));  // (`screen` is the host's only reader of the table)
+// ... and its depth (`screen --depth`): the counters live beside the seen set
+extern "C" int skx_stream_enable_depth(skx_stream* st) __attribute__((weak));
+extern "C" int skx_stream_depth_rows(skx_stream* st, const uint32_t* genomes, uint32_t n, uint32_t* covered, uint32_t* median, uint64_t* total)
+    __attribute__((weak));
 
 namespace sketchy {
 
@@ -324,8 +329,12 @@ class Sketchy {
     // through one table-only stream (top_k = 0: no per-read ranking) with coverage enabled; then, per sketch, covered = its hashes that
     // some read shared, containment = covered / its own size, and the running sum from the table.  The `top` best by containment
     // (ties: the sketch earlier in the file) are printed.  One reference only: several -r are not built.
+    // depth: also the median multiplicity of the printed sketches (the lower median of how many reads shared each covered hash), from
+    // skx_stream_depth_rows of the TOP rows; identity: Mash screen's containment^(1/k), computed here.
     void screen(const std::string& fastx, const std::string& reference, const std::string& genotypes, size_t top, size_t limit, bool header,
-                std::ostream& out) {
+                std::ostream& out, bool depth = false, bool identity = false) {
+        if (depth && !skx_stream_enable_depth) throw UsageError("screen --depth needs skx_stream_enable_depth, which the loaded libsketchy_hip does not export");
+        if (depth && !skx_stream_depth_rows) throw UsageError("screen --depth needs skx_stream_depth_rows, which the loaded libsketchy_hip does not export");
         // there is no host route to the number: a library without the entry points ends here, before anything is read
         if (!skx_stream_enable_coverage) throw SketchyError("screen needs skx_stream_enable_coverage, which the loaded libsketchy_hip does not export");
         if (!skx_stream_coverage) throw SketchyError("screen needs skx_stream_coverage, which the loaded libsketchy_hip does not export");
@@ -345,10 +354,13 @@ class Sketchy {
         const uint64_t max_bases = 1ull << 28;
         skx_stream* st = nullptr;
         hip_check(skx_stream_create(&st, ref.h, 0, (uint32_t)batch_, max_bases), "stream");
-        std::vector<uint32_t> covered(n);
+        std::vector<uint32_t> covered(n), order(n), median(depth ? top : 0);
         std::vector<uint64_t> sum(n);
+        for (size_t g = 0; g < n; ++g) order[g] = (uint32_t)g;
+        auto size_of = [&](uint32_t g) { return (uint64_t)sketches[g].hashes.size(); };
         try {
             hip_check(skx_stream_enable_coverage(st), "screen");
+            if (depth) hip_check(skx_stream_enable_depth(st), "screen");
             FastxReader reader(fastx);
             Batch b; std::string seq;
             size_t reads = 0;
@@ -366,24 +378,30 @@ class Sketchy {
             flush();
             hip_check(skx_stream_coverage(st, covered.data()), "screen");
             hip_check(skx_stream_table(st, sum.data()), "screen");
+            // by containment = covered / size, compared as fractions (exact); an empty sketch contains nothing
+            std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+                return (uint64_t)covered[x] * std::max<uint64_t>(size_of(y), 1) > (uint64_t)covered[y] * std::max<uint64_t>(size_of(x), 1);
+            });
+            if (depth) hip_check(skx_stream_depth_rows(st, order.data(), (uint32_t)top, nullptr, median.data(), nullptr), "screen");
         } catch (...) {
             skx_stream_destroy(st);
             throw;
         }
         skx_stream_destroy(st);
-        // by containment = covered / size, compared as fractions (exact); an empty sketch contains nothing
-        std::vector<uint32_t> order(n);
-        for (size_t g = 0; g < n; ++g) order[g] = (uint32_t)g;
-        auto size_of = [&](uint32_t g) { return (uint64_t)sketches[g].hashes.size(); };
-        std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-            return (uint64_t)covered[x] * std::max<uint64_t>(size_of(y), 1) > (uint64_t)covered[y] * std::max<uint64_t>(size_of(x), 1);
-        });
-        if (header) out << "sketch_id\tcovered\tsketch_size\tcontainment\tshared_hashes" << (with_geno ? "\t" + geno.header : std::string()) << "\n";
+        if (header)
+            out << "sketch_id\tcovered\tsketch_size\tcontainment\tshared_hashes" << (depth ? "\tmedian_multiplicity" : "") << (identity ? "\tidentity" : "")
+                << (with_geno ? "\t" + geno.header : std::string()) << "\n";
         char buf[32];
         for (size_t j = 0; j < top; ++j) {
             const uint32_t g = order[j];
-            std::snprintf(buf, sizeof buf, "%.6f", size_of(g) ? (double)covered[g] / (double)size_of(g) : 0.0);
+            const double containment = size_of(g) ? (double)covered[g] / (double)size_of(g) : 0.0;
+            std::snprintf(buf, sizeof buf, "%.6f", containment);
             out << sketches[g].name << "\t" << covered[g] << "\t" << size_of(g) << "\t" << buf << "\t" << sum[g];
+            if (depth) out << "\t" << median[j];
+            if (identity) {
+                std::snprintf(buf, sizeof buf, "%.6f", std::pow(containment, 1.0 / (double)std::max<uint32_t>(sketches[g].kmer_length, 1u)));
+                out << "\t" << buf;
+            }
             if (with_geno) out << "\t" << join_tab(geno.map.at(sketches[g].name));
             out << "\n";
         }
@@ -1443,10 +1461,12 @@ static void usage() {
                  "                    sketch_id neighbour_id shared_hashes [the neighbour's genotype columns]; -c, with -g and an odd TOP: one line per\n"
                  "                    sketch, the consensus of its neighbours; -S / --summary, with -g: one line per genotype column -- column, the\n"
                  "                    sketches whose own value is that consensus, all sketches)\n"
-                 "sketchy-hip screen  -r REF.msh -i READS.fx[.gz] [-g GENO.tsv] [-t TOP=10] [-l LIMIT] [-H]\n"
+                 "sketchy-hip screen  -r REF.msh -i READS.fx[.gz] [-g GENO.tsv] [-t TOP=10] [-l LIMIT] [-H] [-d] [-I]\n"
                  "                    (containment of every sketch of REF in the read set: the TOP sketches by covered / sketch_size --\n"
-                 "                    sketch_id covered sketch_size containment shared_hashes [genotype columns]; covered = hashes of the sketch that\n"
-                 "                    at least one read shared; one reference: several -r are not built)\n"
+                 "                    sketch_id covered sketch_size containment shared_hashes [median_multiplicity] [identity] [genotype columns];\n"
+                 "                    covered = hashes of the sketch that at least one read shared; -d / --depth: median_multiplicity = the lower\n"
+                 "                    median of the number of reads that shared each covered hash; -I / --identity: containment^(1/k); here -d\n"
+                 "                    is --depth, the device is chosen with --device; one reference: several -r are not built)\n"
                  "sketchy-hip shared  -r REF.msh -q QUERY.msh\n"
                  "sketchy-hip info    -i SKETCH.msh [-p]\n"
                  "sketchy-hip check   -r REF.msh -g GENO.tsv\n");
@@ -1467,6 +1487,8 @@ int main(int argc, char** argv) {
     for (int i = 2; i < argc; ++i) {
         std::string a = argv[i];
         if (is_sketch && a == "--stream") { usage(); return 2; }
+        if (cmd == "screen" && (a == "-d" || a == "--depth")) { flag["--depth"] = true; continue; }  // (`screen`: -d is --depth; the device: --device)
+        if (cmd == "screen" && (a == "-I" || a == "--identity")) { flag["--identity"] = true; continue; }
         if (longnames.count(a)) a = longnames.at(a);
         // (predict: a lone "-" is a path -- stdin)
         if (many_inputs && a == "-i") { while (i + 1 < argc && (argv[i + 1][0] != '-' || (!is_sketch && !argv[i + 1][1]))) inputs.push_back(argv[++i]); continue; }
@@ -1537,7 +1559,8 @@ int main(int argc, char** argv) {
             if (!opt.count("-r") || !opt.count("-i")) { usage(); return 2; }
             const long top = opt.count("-t") ? std::atol(opt["-t"].c_str()) : 10, limit = opt.count("-l") ? std::atol(opt["-l"].c_str()) : 0;
             if (top < 1) { std::fprintf(stderr, "Error: --top must be at least 1\n"); return 2; }
-            app.screen(opt["-i"], opt["-r"], opt.count("-g") ? opt["-g"] : std::string(), (size_t)top, (size_t)std::max(0L, limit), flag["-H"], std::cout);
+            app.screen(opt["-i"], opt["-r"], opt.count("-g") ? opt["-g"] : std::string(), (size_t)top, (size_t)std::max(0L, limit), flag["-H"], std::cout,
+                       flag["--depth"], flag["--identity"]);
         } else if (cmd == "shared") {
             if (!opt.count("-r") || !opt.count("-q")) { usage(); return 2; }
             app.shared(opt["-r"], opt["-q"], std::cout);

@@ -29,6 +29,7 @@
 
 #include "sketchy_hip.h"
 #include "skx_common.hpp"
+#include "skx_genome_groups.hpp"
 #include "skx_kernels.hpp"
 
 using skx::u32;
@@ -1017,6 +1018,48 @@ static const int kSides = kGroupMax + 1;  // copies of the per-batch sketch outp
                                           // (a stream uses stream_coalesce + 1 of them, allocated at first use)
 static const u32 kStagedGroupMax = 4;
 static const int kSlotsMax = 2 * kStagedGroupMax + 1;  // staging slots of the host-fed pipeline
+namespace {
+struct DevMem {  // a device allocation that grows on demand and is freed on every way out of the scope
+    void* p = nullptr; size_t cap = 0;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    hipError_t need(size_t bytes) {
+        if (bytes <= cap && p) return hipSuccess;
+        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
+        if (e == hipSuccess) cap = bytes;
+        return e;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+// The statistics a stream keeps per reference hash: its breadth (skx_stream_enable_coverage) and its depth (skx_stream_enable_depth);
+// everything NULL until enabled.  d_seen = one bit per slot of the reference's key table + two for the lifted hashes, marked on the scan
+// stream behind every pass's classify; d_depth = one saturating u32 per bit, same indices; d_dep_tmp [dep_tmp_n = max(pcap, qcap_max)] = a
+// pass's pairs per position in Q (zero between passes).  The queries' scratch: d_cov_pad = the breadth walk's counts in padded order,
+// d_cov_wide the same widened for the ranking; d_dep_pad = the depth walk's results in padded order, one allocation {total [n_pad] u64,
+// covered, max, median [n_pad] u32}; d_dep_vals = the select's scratch (first query; dep_vals_groups groups of 64 genomes per launch);
+// d_dep_n = two counters of export / import; list = what a query of n genomes needs beside that, {total u64, covered, median, requested
+// genomes, their groups u32} [list_cap] (stats_list_room).
+struct StreamStats {
+    u32* d_seen = nullptr;
+    u32 seen_words = 0;
+    u32* d_cov_pad = nullptr;
+    u64* d_cov_wide = nullptr;
+    u32 *d_depth = nullptr, *d_dep_tmp = nullptr, *d_dep_pad = nullptr, *d_dep_vals = nullptr;
+    unsigned long long* d_dep_n = nullptr;
+    u32 dep_vals_groups = 0, dep_tmp_n = 0;
+    DevMem list;
+    u32 list_cap = 0;
+    u64* l_tot() const { return list.as<u64>(); }
+    u32* l_cov() const { return (u32*)(l_tot() + list_cap); }
+    u32* l_med() const { return l_cov() + list_cap; }
+    u32* l_gen() const { return l_med() + list_cap; }
+    u32* l_grp() const { return l_gen() + list_cap; }
+};
+void stats_free(StreamStats& ss) {  // (the list frees itself)
+    for (void* p : {(void*)ss.d_seen, (void*)ss.d_cov_pad, (void*)ss.d_cov_wide, (void*)ss.d_depth, (void*)ss.d_dep_tmp, (void*)ss.d_dep_pad,
+                    (void*)ss.d_dep_vals, (void*)ss.d_dep_n}) (void)hipFree(p);
+}
+}  // namespace
 struct skx_stream {
     const skx_ref* ref = nullptr;
     int device = 0;
@@ -1262,23 +1305,7 @@ struct skx_stream {
     u32* d_rank_idx = nullptr;  // [n_species][top] outputs of skx_stream_rank
     u64* d_rank_sum = nullptr;
     u32 rank_cap = 0;
-    // breadth of the stream (skx_stream_enable_coverage; all NULL until then): d_seen = one bit per slot of the reference's key table + two
-    // for the lifted hashes, marked on the scan stream behind every pass's classify; the queries' scratch: counts in padded order, the same
-    // widened for the ranking, outputs [n_genomes], {requested genomes, their 64-genome groups, their counts} [3][cov_list_cap], ranked rows [cov_rank_cap]
-    u32* d_seen = nullptr;
-    u32 seen_words = 0;
-    u32 *d_cov_pad = nullptr, *d_cov_out = nullptr, *d_cov_list = nullptr, *d_cov_ridx = nullptr;
-    u64 *d_cov_wide = nullptr, *d_cov_rsum = nullptr;
-    u32 cov_list_cap = 0, cov_rank_cap = 0;
-    // depth of the stream (skx_stream_enable_depth; all NULL until then): d_depth = one saturating u32 per bit of d_seen, same indices; d_dep_tmp
-    // [dep_tmp_n = max(pcap, qcap_max)] = a pass's pairs per position in Q (zero between passes); d_dep_pad = the queries' per-genome results in padded order, one
-    // allocation {covered, max, median [n_pad] u32, total [n_pad] u64}; d_dep_list = {outputs total u64, covered, median, requested genomes,
-    // their groups} [dep_list_cap]; d_dep_vals = the select's scratch (first query; dep_vals_groups groups of 64 genomes per launch);
-    // d_dep_n = two counters of export / import
-    u32 *d_depth = nullptr, *d_dep_tmp = nullptr, *d_dep_pad = nullptr, *d_dep_vals = nullptr;
-    u64* d_dep_list = nullptr;
-    unsigned long long* d_dep_n = nullptr;
-    u32 dep_list_cap = 0, dep_vals_groups = 0, dep_tmp_n = 0;
+    StreamStats stats;       // breadth and depth of the stream
     u32* h_poff = nullptr;   // pinned
     u64* h_offsets = nullptr;  // pinned
     // |Q| / pairs of the most recent pass whose dictionary has finished: the host only knows the pair count of a
@@ -1383,9 +1410,7 @@ static void stream_free(skx_stream* st) {
     for (int i = 1; i < skx_stream::kRankLanes; ++i)
         if (st->own_lane_stream && st->lane[i].s) (void)hipStreamDestroy(st->lane[i].s);
     for (void* p : ptrs) (void)hipFree(p);
-    for (void* p : {(void*)st->d_seen, (void*)st->d_cov_pad, (void*)st->d_cov_out, (void*)st->d_cov_list, (void*)st->d_cov_ridx,
-                    (void*)st->d_cov_wide, (void*)st->d_cov_rsum, (void*)st->d_depth, (void*)st->d_dep_tmp, (void*)st->d_dep_pad,
-                    (void*)st->d_dep_vals, (void*)st->d_dep_list, (void*)st->d_dep_n}) (void)hipFree(p);
+    stats_free(st->stats);
     if (st->h_poff) (void)hipHostFree(st->h_poff);
     if (st->h_offsets) (void)hipHostFree(st->h_offsets);
     if (st->h_nq) (void)hipHostFree(st->h_nq);
@@ -2221,7 +2246,7 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
             skx::launch_classify(hs, d_q, d_nq, q_bound, st->rare_index(), st->d_qinfo, st->d_qloc, st->d_cls_bsum, st->d_qd, d_nd,
                                  st->d_qrow, st->d_sslot, st->h_nd + 2 * b);
             // (a stream with coverage enabled: the pass's distinct hashes that some genome holds are SEEN -- by slot, as classify left them)
-            if (st->d_seen) skx::launch_seen_mark(hs, d_q, d_nq, q_bound, st->d_qinfo, st->d_seen, ref->kt_mask + 1u);
+            if (st->stats.d_seen) skx::launch_seen_mark(hs, d_q, d_nq, q_bound, st->d_qinfo, st->stats.d_seen, ref->kt_mask + 1u);
             scan_q = st->d_qd; scan_nq = d_nd;
         } else {
             skx::launch_nd_from_nq(hs, d_nq, d_nd, st->h_nd + 2 * b);
@@ -2268,9 +2293,9 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
         if (P > 0) {
             skx::launch_pair_q(hs, st->d_pair_h[b], P, d_q, d_nq, d_pair_q, split_dict ? st->d_qrow : nullptr, st->d_bbase, st->d_btot, ref->max_ref);
             // (a stream with depth enabled: every (read, hash) pair of the pass counts once for its hash -- while the pair hashes are still here)
-            if (st->d_depth && split_dict)
-                skx::launch_depth_mark(hs, st->d_pair_h[b], P, d_q, d_nq, q_bound, st->d_qinfo, st->d_bbase, st->d_btot, ref->max_ref, st->d_dep_tmp,
-                                       st->d_depth, ref->kt_mask + 1u);
+            if (st->stats.d_depth && split_dict)
+                skx::launch_depth_mark(hs, st->d_pair_h[b], P, d_q, d_nq, q_bound, st->d_qinfo, st->d_bbase, st->d_btot, ref->max_ref, st->stats.d_dep_tmp,
+                                       st->stats.d_depth, ref->kt_mask + 1u);
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(st->ev_pairq[b], hs));  // the set's hash set and pair hashes may be refilled
@@ -4209,6 +4234,15 @@ SKX_API int skx_stream_table_add(skx_stream* st, const uint64_t* add) {
     HIPCHK(hipStreamSynchronize(st->hs2));  // `add` is only borrowed for the call
     return SKX_OK;
 }
+// a new sample has seen nothing and counted nothing; what was enabled stays enabled
+static int stats_reset(StreamStats& ss, u32 kt_mask, hipStream_t on) {
+    if (ss.d_seen) HIPCHK(hipMemsetAsync(ss.d_seen, 0, (size_t)ss.seen_words * 4, on));
+    if (ss.d_depth) {
+        HIPCHK(hipMemsetAsync(ss.d_depth, 0, ((size_t)kt_mask + 3u) * 4, on));
+        HIPCHK(hipMemsetAsync(ss.d_dep_tmp, 0, (size_t)ss.dep_tmp_n * 4, on));
+    }
+    return SKX_OK;
+}
 SKX_API int skx_stream_reset(skx_stream* st) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
     SKXCHK(use_device(st->device));
@@ -4217,11 +4251,7 @@ SKX_API int skx_stream_reset(skx_stream* st) {
     HIPCHK(hipStreamSynchronize(st->hs1));
     HIPCHK(hipStreamSynchronize(st->hs));
     HIPCHK(hipMemsetAsync(st->d_cum, 0, (size_t)st->ref->n_pad * 8, st->hs2));
-    if (st->d_seen) HIPCHK(hipMemsetAsync(st->d_seen, 0, (size_t)st->seen_words * 4, st->hs2));  // (a new sample has seen nothing; coverage stays enabled)
-    if (st->d_depth) {  // (... and counted nothing; depth stays enabled)
-        HIPCHK(hipMemsetAsync(st->d_depth, 0, ((size_t)st->ref->kt_mask + 3u) * 4, st->hs2));
-        HIPCHK(hipMemsetAsync(st->d_dep_tmp, 0, (size_t)st->dep_tmp_n * 4, st->hs2));
-    }
+    SKXCHK(stats_reset(st->stats, st->ref->kt_mask, st->hs2));
     HIPCHK(hipStreamSynchronize(st->hs2));
     st->reads_total = 0;
     st->h_nq[2] = 1; st->h_nq[3] = 1;  // (a new sample: every genome is a candidate again)
@@ -4261,27 +4291,36 @@ SKX_API int skx_stream_stats(skx_stream* st, uint64_t* out, uint32_t n_out) {
     for (uint32_t i = 0; i < n_out; ++i) out[i] = i < SKX_N_STATS ? v[i] : 0;
     return SKX_OK;
 }
-SKX_API int skx_stream_rank(skx_stream* st, uint32_t top_k, uint32_t* idx, uint64_t* sum) {
-    if (!st || !idx || !sum) return fail(SKX_ERR_INVALID, "NULL argument");
+// The first top_k rows per species of a padded u64 table, ranked on stream `on` (behind what the caller queued there) in the stream's ONE
+// ranking scratch and copied to idx / sum [n_species][top_k].  Both callers (skx_stream_rank on hs2, skx_stream_coverage_rank on hs)
+// are synchronous, and this waits for `on` on every way out once something is queued: whichever stream the next call queues on, the
+// scratch is idle when it grows or fills it again.
+static int rank_padded(skx_stream* st, hipStream_t on, const u64* d_table, u32 top_k, uint32_t* idx, uint64_t* sum) {
     const skx_ref* ref = st->ref;
-    if (top_k < 1 || top_k > ref->min_species) return fail(SKX_ERR_INVALID, "top_k=%u outside 1..n_genomes", top_k);
-    SKXCHK(use_device(st->device));
-    SKXCHK(flush_pending(st));
     const size_t rows = (size_t)ref->n_species * top_k;
     if (rows > st->rank_cap) {  // (beyond SKX_MAX_TOP rows per species: grow the scratch once)
-        HIPCHK(hipStreamSynchronize(st->hs2));
+        HIPCHK(hipStreamSynchronize(on));
         (void)hipFree(st->d_rank_idx); (void)hipFree(st->d_rank_sum);
         st->d_rank_idx = nullptr; st->d_rank_sum = nullptr; st->rank_cap = 0;
         HIPCHK(hipMalloc(&st->d_rank_idx, rows * 4));
         HIPCHK(hipMalloc(&st->d_rank_sum, rows * 8));
         st->rank_cap = (u32)rows;
     }
-    skx::launch_rank_table(st->hs2, st->d_cum, ref->species(), top_k, st->d_rank_idx, st->d_rank_sum);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(idx, st->d_rank_idx, rows * 4, hipMemcpyDeviceToHost, st->hs2));
-    HIPCHK(hipMemcpyAsync(sum, st->d_rank_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
-    HIPCHK(hipStreamSynchronize(st->hs2));
+    skx::launch_rank_table(on, d_table, ref->species(), top_k, st->d_rank_idx, st->d_rank_sum);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(idx, st->d_rank_idx, rows * 4, hipMemcpyDeviceToHost, on);
+    if (e == hipSuccess) e = hipMemcpyAsync(sum, st->d_rank_sum, rows * 8, hipMemcpyDeviceToHost, on);
+    const hipError_t e2 = hipStreamSynchronize(on);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(SKX_ERR_HIP, "ranking a table failed: %s", hipGetErrorString(e));
     return SKX_OK;
+}
+SKX_API int skx_stream_rank(skx_stream* st, uint32_t top_k, uint32_t* idx, uint64_t* sum) {
+    if (!st || !idx || !sum) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (top_k < 1 || top_k > st->ref->min_species) return fail(SKX_ERR_INVALID, "top_k=%u outside 1..n_genomes", top_k);
+    SKXCHK(use_device(st->device));
+    SKXCHK(flush_pending(st));
+    return rank_padded(st, st->hs2, st->d_cum, top_k, idx, sum);
 }
 
 // ------------------------------------------------------------------ breadth of a stream
@@ -4289,124 +4328,48 @@ SKX_API int skx_stream_rank(skx_stream* st, uint32_t top_k, uint32_t* idx, uint6
 // stream (run_pass_multi, behind the pass's classify); the queries run there too, behind them, and walk the resident matrix against the
 // bitmap.  ONE walk kernel serves the whole table and a list of genomes: its unit of work is an aligned group of 64 padded genomes -- a
 // list launches the groups that hold a requested genome and nothing else (16 scattered genomes: 16 groups of the 625 at 40 000).
-SKX_API int skx_stream_enable_coverage(skx_stream* st) {
-    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
-    if (st->d_seen) return SKX_OK;
-    const skx_ref* ref = st->ref;
-    if (!ref->d_kt_key)
-        return fail(SKX_ERR_UNSUPPORTED, "skx_stream_enable_coverage: the reference has no rare-hash index (policy rare_hash_genomes = 0): nothing gives a "
-                                         "query hash a persistent identity");
+// what enabling a statistic asks of the stream (fn: the entry point, for the messages)
+static int stats_can_enable(skx_stream* st, const char* fn) {
+    if (!st->ref->d_kt_key)
+        return fail(SKX_ERR_UNSUPPORTED, "%s: the reference has no rare-hash index (policy rare_hash_genomes = 0): nothing gives a "
+                                         "query hash a persistent identity", fn);
     uint64_t reads = 0;
     SKXCHK(skx_stream_reads(st, &reads));
-    if (reads) return fail(SKX_ERR_INVALID, "skx_stream_enable_coverage: the stream has taken %llu reads already (enable it first, or after a reset)",
+    if (reads) return fail(SKX_ERR_INVALID, "%s: the stream has taken %llu reads already (enable it first, or after a reset)", fn,
                            (unsigned long long)reads);
-    SKXCHK(use_device(st->device));
+    return use_device(st->device);
+}
+SKX_API int skx_stream_enable_coverage(skx_stream* st) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    StreamStats& ss = st->stats;
+    if (ss.d_seen) return SKX_OK;
+    SKXCHK(stats_can_enable(st, "skx_stream_enable_coverage"));
+    const skx_ref* ref = st->ref;
     const u32 words = (u32)(((u64)ref->kt_mask + 1u + 2u + 31u) / 32u);
-    u32 *seen = nullptr, *pad = nullptr, *out = nullptr;
+    u32 *seen = nullptr, *pad = nullptr;
     u64* wide = nullptr;
     hipError_t e = hipMalloc(&seen, (size_t)words * 4);
     if (e == hipSuccess) e = hipMalloc(&pad, (size_t)ref->n_pad * 4);
-    if (e == hipSuccess) e = hipMalloc(&out, (size_t)ref->n_genomes * 4);
     if (e == hipSuccess) e = hipMalloc(&wide, (size_t)ref->n_pad * 8);
     if (e == hipSuccess) e = hipMemset(seen, 0, (size_t)words * 4);
     if (e != hipSuccess) {  // (all or nothing: the stream is left as it was)
-        (void)hipFree(seen); (void)hipFree(pad); (void)hipFree(out); (void)hipFree(wide);
+        (void)hipFree(seen); (void)hipFree(pad); (void)hipFree(wide);
         (void)hipGetLastError();
         return fail(SKX_ERR_HIP, "skx_stream_enable_coverage: %s", hipGetErrorString(e));
     }
-    st->d_cov_pad = pad; st->d_cov_out = out; st->d_cov_wide = wide; st->seen_words = words;
-    st->d_seen = seen;
+    ss.d_cov_pad = pad; ss.d_cov_wide = wide; ss.seen_words = words;
+    ss.d_seen = seen;
     return SKX_OK;
 }
 // count on the scan stream, behind the marks of every pass queued so far (the caller has flushed): groups == NULL -> every group of 64
-// padded genomes
-static int coverage_walk(skx_stream* st, const u32* d_groups, u32 n_groups) {
+// padded genomes.  Leaves the counts of the walked genomes in d_cov_pad.
+static hipError_t coverage_walk(skx_stream* st, const u32* d_groups, u32 n_groups) {
     const skx_ref* ref = st->ref;
-    HIPCHK(hipMemsetAsync(st->d_cov_pad, 0, (size_t)ref->n_pad * 4, st->hs));
-    skx::launch_coverage_walk(st->hs, ref->d_mat, ref->s, d_groups, d_groups ? n_groups : ref->n_pad / 64u, ref->d_kt_key, ref->kt_mask, st->d_seen,
-                              ref->d_exc_g, ref->d_exc_h, ref->n_exc, st->d_cov_pad);
-    HIPCHK(hipGetLastError());
-    return SKX_OK;
-}
-SKX_API int skx_stream_coverage(skx_stream* st, uint32_t* covered) {
-    if (!st || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
-    if (!st->d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage: coverage was never enabled on this stream");
-    SKXCHK(use_device(st->device));
-    const skx_ref* ref = st->ref;
-    SKXCHK(flush_pending(st));
-    SKXCHK(coverage_walk(st, nullptr, 0));
-    skx::launch_coverage_gather(st->hs, st->d_cov_pad, ref->d_real2pad, nullptr, ref->n_genomes, st->d_cov_out);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(covered, st->d_cov_out, (size_t)ref->n_genomes * 4, hipMemcpyDeviceToHost, st->hs));
-    HIPCHK(hipStreamSynchronize(st->hs));
-    return SKX_OK;
-}
-SKX_API int skx_stream_coverage_rows(skx_stream* st, const uint32_t* genomes, uint32_t n, uint32_t* covered) {
-    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
-    if (!st->d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rows: coverage was never enabled on this stream");
-    if (n == 0) return SKX_OK;
-    if (!genomes || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
-    const skx_ref* ref = st->ref;
-    for (u32 i = 0; i < n; ++i)
-        if (genomes[i] >= ref->n_genomes) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rows: genomes[%u] = %u outside 0..n_genomes - 1 = %u", i, genomes[i], ref->n_genomes - 1);
-    SKXCHK(use_device(st->device));
-    // the aligned 64-genome groups (padded order) that hold a requested genome, each once
-    std::vector<u32> grp(n);
-    for (u32 i = 0; i < n; ++i) {
-        u32 sp = 0;
-        while (sp + 1 < ref->n_species && genomes[i] >= ref->sp_real0[sp + 1]) ++sp;
-        grp[i] = (ref->sp_g0[sp] + (genomes[i] - ref->sp_real0[sp])) / 64u;
-    }
-    std::sort(grp.begin(), grp.end());
-    grp.erase(std::unique(grp.begin(), grp.end()), grp.end());
-    SKXCHK(flush_pending(st));
-    if (n > st->cov_list_cap) {  // (list, groups and outputs: one allocation of three parts, grown to the longest list asked for)
-        HIPCHK(hipStreamSynchronize(st->hs));
-        (void)hipFree(st->d_cov_list);
-        st->d_cov_list = nullptr; st->cov_list_cap = 0;
-        const u32 cap = std::max<u32>(n, 64u);
-        HIPCHK(hipMalloc(&st->d_cov_list, (size_t)cap * 3 * 4));
-        st->cov_list_cap = cap;
-    }
-    u32 *d_grp = st->d_cov_list + st->cov_list_cap, *d_out = d_grp + st->cov_list_cap;
-    HIPCHK(hipMemcpyAsync(st->d_cov_list, genomes, (size_t)n * 4, hipMemcpyHostToDevice, st->hs));
-    HIPCHK(hipMemcpyAsync(d_grp, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, st->hs));
-    int rc = coverage_walk(st, d_grp, (u32)grp.size());
-    if (rc == SKX_OK) {
-        skx::launch_coverage_gather(st->hs, st->d_cov_pad, ref->d_real2pad, st->d_cov_list, n, d_out);
-        if (hipGetLastError() != hipSuccess || hipMemcpyAsync(covered, d_out, (size_t)n * 4, hipMemcpyDeviceToHost, st->hs) != hipSuccess)
-            rc = fail(SKX_ERR_HIP, "skx_stream_coverage_rows: %s", hipGetErrorString(hipGetLastError()));
-    }
-    const hipError_t e = hipStreamSynchronize(st->hs);  // (`genomes` and the group list are only borrowed until here, on every way out)
-    if (rc == SKX_OK && e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_stream_coverage_rows: %s", hipGetErrorString(e));
-    return rc;
-}
-SKX_API int skx_stream_coverage_rank(skx_stream* st, uint32_t top_k, uint32_t* idx, uint32_t* covered) {
-    if (!st || !idx || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
-    if (!st->d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rank: coverage was never enabled on this stream");
-    const skx_ref* ref = st->ref;
-    if (top_k < 1 || top_k > ref->min_species) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rank: top_k=%u outside 1..%u (the smallest species)", top_k, ref->min_species);
-    SKXCHK(use_device(st->device));
-    const size_t rows = (size_t)ref->n_species * top_k;
-    SKXCHK(flush_pending(st));
-    if (rows > st->cov_rank_cap) {
-        HIPCHK(hipStreamSynchronize(st->hs));
-        (void)hipFree(st->d_cov_ridx); (void)hipFree(st->d_cov_rsum);
-        st->d_cov_ridx = nullptr; st->d_cov_rsum = nullptr; st->cov_rank_cap = 0;
-        HIPCHK(hipMalloc(&st->d_cov_ridx, rows * 4));
-        HIPCHK(hipMalloc(&st->d_cov_rsum, rows * 8));
-        st->cov_rank_cap = (u32)rows;
-    }
-    SKXCHK(coverage_walk(st, nullptr, 0));
-    skx::launch_coverage_widen(st->hs, st->d_cov_pad, ref->n_pad, st->d_cov_wide);
-    skx::launch_rank_table(st->hs, st->d_cov_wide, ref->species(), top_k, st->d_cov_ridx, st->d_cov_rsum);
-    HIPCHK(hipGetLastError());
-    std::vector<u64> sum(rows);
-    HIPCHK(hipMemcpyAsync(idx, st->d_cov_ridx, rows * 4, hipMemcpyDeviceToHost, st->hs));
-    HIPCHK(hipMemcpyAsync(sum.data(), st->d_cov_rsum, rows * 8, hipMemcpyDeviceToHost, st->hs));
-    HIPCHK(hipStreamSynchronize(st->hs));
-    for (size_t i = 0; i < rows; ++i) covered[i] = (u32)sum[i];
-    return SKX_OK;
+    const hipError_t e = hipMemsetAsync(st->stats.d_cov_pad, 0, (size_t)ref->n_pad * 4, st->hs);
+    if (e != hipSuccess) return e;
+    skx::launch_coverage_walk(st->hs, ref->d_mat, ref->s, d_groups, d_groups ? n_groups : ref->n_pad / 64u, ref->d_kt_key, ref->kt_mask,
+                              st->stats.d_seen, ref->d_exc_g, ref->d_exc_h, ref->n_exc, st->stats.d_cov_pad);
+    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ depth of a stream
@@ -4416,17 +4379,11 @@ SKX_API int skx_stream_coverage_rank(skx_stream* st, uint32_t top_k, uint32_t* i
 constexpr size_t kDepthScratch = (size_t)256 << 20;
 SKX_API int skx_stream_enable_depth(skx_stream* st) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
-    if (st->d_depth) return SKX_OK;
-    const skx_ref* ref = st->ref;
-    if (!ref->d_kt_key)
-        return fail(SKX_ERR_UNSUPPORTED, "skx_stream_enable_depth: the reference has no rare-hash index (policy rare_hash_genomes = 0): nothing gives a "
-                                         "query hash a persistent identity");
-    uint64_t reads = 0;
-    SKXCHK(skx_stream_reads(st, &reads));
-    if (reads) return fail(SKX_ERR_INVALID, "skx_stream_enable_depth: the stream has taken %llu reads already (enable it first, or after a reset)",
-                           (unsigned long long)reads);
+    StreamStats& ss = st->stats;
+    if (ss.d_depth) return SKX_OK;
+    SKXCHK(stats_can_enable(st, "skx_stream_enable_depth"));
     SKXCHK(skx_stream_enable_coverage(st));  // (the bitmap stays the truth for `covered`; enabled already: nothing happens)
-    SKXCHK(use_device(st->device));
+    const skx_ref* ref = st->ref;
     const size_t n_ctr = (size_t)ref->kt_mask + 3u;
     u32 *depth = nullptr, *tmp = nullptr, *pad = nullptr;
     unsigned long long* ctr = nullptr;
@@ -4442,102 +4399,134 @@ SKX_API int skx_stream_enable_depth(skx_stream* st) {
         (void)hipGetLastError();
         return fail(SKX_ERR_HIP, "skx_stream_enable_depth: %s", hipGetErrorString(e));
     }
-    st->d_dep_tmp = tmp; st->dep_tmp_n = tmp_n; st->d_dep_pad = pad; st->d_dep_n = ctr;
-    st->d_depth = depth;
-    return SKX_OK;
-}
-// {total u64, covered, median, genomes, groups u32} [dep_list_cap], one allocation grown to the longest list asked for
-static int depth_list_room(skx_stream* st, u32 n) {
-    if (n <= st->dep_list_cap) return SKX_OK;
-    HIPCHK(hipStreamSynchronize(st->hs));
-    (void)hipFree(st->d_dep_list);
-    st->d_dep_list = nullptr; st->dep_list_cap = 0;
-    const u32 cap = std::max<u32>(n, 64u);
-    HIPCHK(hipMalloc(&st->d_dep_list, (size_t)cap * 24));
-    st->dep_list_cap = cap;
+    ss.d_dep_tmp = tmp; ss.dep_tmp_n = tmp_n; ss.d_dep_pad = pad; ss.d_dep_n = ctr;
+    ss.d_depth = depth;
     return SKX_OK;
 }
 // walk and select on the scan stream, behind the counts of every pass queued so far (the caller has flushed): d_groups == NULL -> every
-// group of 64 padded genomes.  Leaves covered / max / median / total of the walked genomes in d_dep_pad.
-static int depth_walk(skx_stream* st, const u32* d_groups, u32 n_groups) {
+// group of 64 padded genomes.  Leaves total / covered / max / median of the walked genomes in d_dep_pad.
+static hipError_t depth_walk(skx_stream* st, const u32* d_groups, u32 n_groups) {
     const skx_ref* ref = st->ref;
+    StreamStats& ss = st->stats;
     const u32 n_pad = ref->n_pad;
     if (!d_groups) n_groups = n_pad / 64u;
-    if (!st->d_dep_vals) {  // (first query: as many groups per launch as the budget holds, never more than the table has)
+    hipError_t e = hipSuccess;
+    if (!ss.d_dep_vals) {  // (first query: as many groups per launch as the budget holds, never more than the table has)
         size_t budget = kDepthScratch;
         if (const char* k = skx::knob("SKX_DEPTH_SCRATCH")) budget = (size_t)strtoull(k, nullptr, 10);  // experiment knob: bytes
         const size_t per = skx::depth_vals_per_group(ref->s) * 4;
         const u32 g = (u32)std::min<size_t>(std::max<size_t>(budget / per, 1), n_pad / 64u);
-        HIPCHK(hipMalloc(&st->d_dep_vals, per * g));
-        st->dep_vals_groups = g;
+        if ((e = hipMalloc(&ss.d_dep_vals, per * g)) != hipSuccess) return e;
+        ss.dep_vals_groups = g;
     }
-    u64* d_tot = (u64*)st->d_dep_pad;
-    u32 *d_cov = st->d_dep_pad + 2 * (size_t)n_pad, *d_max = d_cov + n_pad, *d_med = d_max + n_pad;
-    HIPCHK(hipMemsetAsync(st->d_dep_pad, 0, (size_t)n_pad * 20, st->hs));
-    for (u32 g0 = 0; g0 < n_groups; g0 += st->dep_vals_groups) {  // (launches on one stream: a chunk's select is through before the next walk)
-        const u32 cnt = std::min(st->dep_vals_groups, n_groups - g0);
-        skx::launch_depth_walk(st->hs, ref->d_mat, ref->s, d_groups ? d_groups + g0 : nullptr, g0, cnt, ref->d_kt_key, ref->kt_mask, st->d_depth,
-                               ref->d_exc_g, ref->d_exc_h, ref->n_exc, d_cov, d_tot, d_max, d_med, st->d_dep_vals);
+    u64* d_tot = (u64*)ss.d_dep_pad;
+    u32 *d_cov = ss.d_dep_pad + 2 * (size_t)n_pad, *d_max = d_cov + n_pad, *d_med = d_max + n_pad;
+    if ((e = hipMemsetAsync(ss.d_dep_pad, 0, (size_t)n_pad * 20, st->hs)) != hipSuccess) return e;
+    for (u32 g0 = 0; g0 < n_groups; g0 += ss.dep_vals_groups) {  // (launches on one stream: a chunk's select is through before the next walk)
+        const u32 cnt = std::min(ss.dep_vals_groups, n_groups - g0);
+        skx::launch_depth_walk(st->hs, ref->d_mat, ref->s, d_groups ? d_groups + g0 : nullptr, g0, cnt, ref->d_kt_key, ref->kt_mask, ss.d_depth,
+                               ref->d_exc_g, ref->d_exc_h, ref->n_exc, d_cov, d_tot, d_max, d_med, ss.d_dep_vals);
     }
-    HIPCHK(hipGetLastError());
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the queries of both statistics
+// ONE allocation for what a query of n genomes needs beside the walk's padded results, used by the list and the whole-table queries of
+// both statistics and grown to the longest list asked for (at least 64).  Every query waits for the scan stream before it returns; the
+// stream is waited for once more before a grow frees the old allocation.
+static int stats_list_room(skx_stream* st, u32 n) {
+    StreamStats& ss = st->stats;
+    if (n <= ss.list_cap) return SKX_OK;
+    HIPCHK(hipStreamSynchronize(st->hs));
+    ss.list_cap = 0;
+    const u32 cap = std::max<u32>(n, 64u);
+    HIPCHK(ss.list.need((size_t)cap * 24));
+    ss.list_cap = cap;
     return SKX_OK;
 }
-// gather for n genomes (d_genomes == NULL: genomes 0 .. n - 1) and copy what the caller wants; waits for the stream
-static int depth_results(skx_stream* st, const u32* d_genomes, u32 n, uint32_t* covered, uint32_t* median, uint64_t* total) {
+// One query (fn: the entry point, for the messages): depth or breadth, of the n listed genomes (any order, repeats allowed: the aligned
+// 64-genome groups that hold one are walked, each once) or, genomes == NULL, of the whole table.  Walk, gather, copy what the caller
+// wants (an output that is NULL is not wanted) -- and once anything is queued ALWAYS wait for the scan stream, on every way out: the
+// caller's arrays and the group list are only borrowed until then.  The first error is the one reported.
+static int stats_query(skx_stream* st, const char* fn, bool depth, const uint32_t* genomes, u32 n, uint32_t* covered, uint32_t* median,
+                       uint64_t* total) {
     const skx_ref* ref = st->ref;
-    const u32 n_pad = ref->n_pad, cap = st->dep_list_cap;
-    const u64* d_tot = (const u64*)st->d_dep_pad;
-    const u32 *d_cov = st->d_dep_pad + 2 * (size_t)n_pad, *d_med = d_cov + 2 * (size_t)n_pad;
-    u64* o_tot = st->d_dep_list;
-    u32 *o_cov = (u32*)(st->d_dep_list + cap), *o_med = o_cov + cap;
-    skx::launch_depth_gather(st->hs, d_cov, d_med, d_tot, ref->d_real2pad, d_genomes, n, o_cov, o_med, o_tot);
-    HIPCHK(hipGetLastError());
-    if (covered) HIPCHK(hipMemcpyAsync(covered, o_cov, (size_t)n * 4, hipMemcpyDeviceToHost, st->hs));
-    if (median) HIPCHK(hipMemcpyAsync(median, o_med, (size_t)n * 4, hipMemcpyDeviceToHost, st->hs));
-    if (total) HIPCHK(hipMemcpyAsync(total, o_tot, (size_t)n * 8, hipMemcpyDeviceToHost, st->hs));
+    StreamStats& ss = st->stats;
+    std::vector<u32> grp;
+    if (genomes) {
+        const u32 bad = skx::genome_groups(ref->n_species, ref->sp_real0.data(), ref->sp_g0.data(), ref->n_genomes, genomes, n, grp);
+        if (bad < n) return fail(SKX_ERR_INVALID, "%s: genomes[%u] = %u outside 0..n_genomes - 1 = %u", fn, bad, genomes[bad], ref->n_genomes - 1);
+    } else n = ref->n_genomes;
+    SKXCHK(use_device(st->device));
+    SKXCHK(flush_pending(st));
+    SKXCHK(stats_list_room(st, n));
+    hipError_t e = hipSuccess;
+    if (genomes) {
+        e = hipMemcpyAsync(ss.l_gen(), genomes, (size_t)n * 4, hipMemcpyHostToDevice, st->hs);
+        if (e == hipSuccess) e = hipMemcpyAsync(ss.l_grp(), grp.data(), grp.size() * 4, hipMemcpyHostToDevice, st->hs);
+    }
+    const u32* d_grp = genomes ? ss.l_grp() : nullptr;
+    if (e == hipSuccess) e = depth ? depth_walk(st, d_grp, (u32)grp.size()) : coverage_walk(st, d_grp, (u32)grp.size());
+    if (e == hipSuccess) {
+        const u32 n_pad = ref->n_pad;
+        const u64* d_tot = depth ? (const u64*)ss.d_dep_pad : nullptr;
+        const u32 *d_cov = depth ? ss.d_dep_pad + 2 * (size_t)n_pad : ss.d_cov_pad, *d_med = depth ? d_cov + 2 * (size_t)n_pad : nullptr;
+        skx::launch_genome_gather(st->hs, d_cov, d_med, d_tot, ref->d_real2pad, genomes ? ss.l_gen() : nullptr, n,
+                                  covered ? ss.l_cov() : nullptr, median ? ss.l_med() : nullptr, total ? ss.l_tot() : nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && covered) e = hipMemcpyAsync(covered, ss.l_cov(), (size_t)n * 4, hipMemcpyDeviceToHost, st->hs);
+    if (e == hipSuccess && median) e = hipMemcpyAsync(median, ss.l_med(), (size_t)n * 4, hipMemcpyDeviceToHost, st->hs);
+    if (e == hipSuccess && total) e = hipMemcpyAsync(total, ss.l_tot(), (size_t)n * 8, hipMemcpyDeviceToHost, st->hs);
+    const hipError_t e2 = hipStreamSynchronize(st->hs);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(SKX_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return SKX_OK;
+}
+SKX_API int skx_stream_coverage(skx_stream* st, uint32_t* covered) {
+    if (!st || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st->stats.d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage: coverage was never enabled on this stream");
+    return stats_query(st, "skx_stream_coverage", false, nullptr, 0, covered, nullptr, nullptr);
+}
+SKX_API int skx_stream_coverage_rows(skx_stream* st, const uint32_t* genomes, uint32_t n, uint32_t* covered) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (!st->stats.d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rows: coverage was never enabled on this stream");
+    if (n == 0) return SKX_OK;
+    if (!genomes || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
+    return stats_query(st, "skx_stream_coverage_rows", false, genomes, n, covered, nullptr, nullptr);
+}
+SKX_API int skx_stream_coverage_rank(skx_stream* st, uint32_t top_k, uint32_t* idx, uint32_t* covered) {
+    if (!st || !idx || !covered) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st->stats.d_seen) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rank: coverage was never enabled on this stream");
+    const skx_ref* ref = st->ref;
+    if (top_k < 1 || top_k > ref->min_species) return fail(SKX_ERR_INVALID, "skx_stream_coverage_rank: top_k=%u outside 1..%u (the smallest species)", top_k, ref->min_species);
+    SKXCHK(use_device(st->device));
+    SKXCHK(flush_pending(st));
+    hipError_t e = coverage_walk(st, nullptr, 0);
+    if (e == hipSuccess) {
+        skx::launch_coverage_widen(st->hs, st->stats.d_cov_pad, ref->n_pad, st->stats.d_cov_wide);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st->hs);
+        return fail(SKX_ERR_HIP, "skx_stream_coverage_rank: %s", hipGetErrorString(e));
+    }
+    std::vector<uint64_t> sum((size_t)ref->n_species * top_k);
+    SKXCHK(rank_padded(st, st->hs, st->stats.d_cov_wide, top_k, idx, sum.data()));
+    for (size_t i = 0; i < sum.size(); ++i) covered[i] = (u32)sum[i];
     return SKX_OK;
 }
 SKX_API int skx_stream_depth(skx_stream* st, uint32_t* covered, uint32_t* median, uint64_t* total) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
-    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth: depth was never enabled on this stream");
-    SKXCHK(use_device(st->device));
-    const skx_ref* ref = st->ref;
-    SKXCHK(flush_pending(st));
-    SKXCHK(depth_list_room(st, ref->n_genomes));
-    int rc = depth_walk(st, nullptr, 0);
-    if (rc == SKX_OK) rc = depth_results(st, nullptr, ref->n_genomes, covered, median, total);
-    const hipError_t e = hipStreamSynchronize(st->hs);
-    if (rc == SKX_OK && e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_stream_depth: %s", hipGetErrorString(e));
-    return rc;
+    if (!st->stats.d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth: depth was never enabled on this stream");
+    return stats_query(st, "skx_stream_depth", true, nullptr, 0, covered, median, total);
 }
 SKX_API int skx_stream_depth_rows(skx_stream* st, const uint32_t* genomes, uint32_t n, uint32_t* covered, uint32_t* median, uint64_t* total) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
-    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_rows: depth was never enabled on this stream");
+    if (!st->stats.d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_rows: depth was never enabled on this stream");
     if (n == 0) return SKX_OK;
     if (!genomes) return fail(SKX_ERR_INVALID, "NULL argument");
-    const skx_ref* ref = st->ref;
-    for (u32 i = 0; i < n; ++i)
-        if (genomes[i] >= ref->n_genomes) return fail(SKX_ERR_INVALID, "skx_stream_depth_rows: genomes[%u] = %u outside 0..n_genomes - 1 = %u", i, genomes[i], ref->n_genomes - 1);
-    SKXCHK(use_device(st->device));
-    // the aligned 64-genome groups (padded order) that hold a requested genome, each once
-    std::vector<u32> grp(n);
-    for (u32 i = 0; i < n; ++i) {
-        u32 sp = 0;
-        while (sp + 1 < ref->n_species && genomes[i] >= ref->sp_real0[sp + 1]) ++sp;
-        grp[i] = (ref->sp_g0[sp] + (genomes[i] - ref->sp_real0[sp])) / 64u;
-    }
-    std::sort(grp.begin(), grp.end());
-    grp.erase(std::unique(grp.begin(), grp.end()), grp.end());
-    SKXCHK(flush_pending(st));
-    SKXCHK(depth_list_room(st, n));
-    u32 *d_gen = (u32*)(st->d_dep_list + st->dep_list_cap) + 2 * (size_t)st->dep_list_cap, *d_grp = d_gen + st->dep_list_cap;
-    HIPCHK(hipMemcpyAsync(d_gen, genomes, (size_t)n * 4, hipMemcpyHostToDevice, st->hs));
-    HIPCHK(hipMemcpyAsync(d_grp, grp.data(), grp.size() * 4, hipMemcpyHostToDevice, st->hs));
-    int rc = depth_walk(st, d_grp, (u32)grp.size());
-    if (rc == SKX_OK) rc = depth_results(st, d_gen, n, covered, median, total);
-    const hipError_t e = hipStreamSynchronize(st->hs);  // (`genomes` and the group list are only borrowed until here, on every way out)
-    if (rc == SKX_OK && e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_stream_depth_rows: %s", hipGetErrorString(e));
-    return rc;
+    return stats_query(st, "skx_stream_depth_rows", true, genomes, n, covered, median, total);
 }
 // ---- portable state: (hash, count), keyed by the hash because the key table's slot layout is not reproducible between two builds
 static int depth_export_run(skx_stream* st, uint64_t* hashes, uint32_t* counts, uint64_t cap, uint64_t* n) {
@@ -4546,65 +4535,64 @@ static int depth_export_run(skx_stream* st, uint64_t* hashes, uint32_t* counts, 
     SKXCHK(use_device(st->device));
     SKXCHK(flush_pending(st));
     unsigned long long have = 0;
-    HIPCHK(hipMemsetAsync(st->d_dep_n, 0, 16, st->hs));
-    skx::launch_depth_export(st->hs, ref->d_kt_key, st->d_depth, slots, nullptr, nullptr, 0, st->d_dep_n);
+    HIPCHK(hipMemsetAsync(st->stats.d_dep_n, 0, 16, st->hs));
+    skx::launch_depth_export(st->hs, ref->d_kt_key, st->stats.d_depth, slots, nullptr, nullptr, 0, st->stats.d_dep_n);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&have, st->d_dep_n, 8, hipMemcpyDeviceToHost, st->hs));
+    HIPCHK(hipMemcpyAsync(&have, st->stats.d_dep_n, 8, hipMemcpyDeviceToHost, st->hs));
     HIPCHK(hipStreamSynchronize(st->hs));
     *n = have;
     const u64 take = std::min<u64>(have, hashes ? cap : 0);
     if (take == 0) return SKX_OK;
-    u64* d_h = nullptr;  // (a call's own buffers: hashes u64 [take], counts u32 [take])
-    HIPCHK(hipMalloc(&d_h, (size_t)take * 12));
+    DevMem m;  // (a call's own buffers: hashes u64 [take], counts u32 [take]; the stream is idle on every way out)
+    HIPCHK(m.need((size_t)take * 12));
+    u64* d_h = m.as<u64>();
     u32* d_c = (u32*)(d_h + take);
-    int rc = SKX_OK;
-    hipError_t e = hipMemsetAsync(st->d_dep_n + 1, 0, 8, st->hs);
+    hipError_t e = hipMemsetAsync(st->stats.d_dep_n + 1, 0, 8, st->hs);
     if (e == hipSuccess) {
-        skx::launch_depth_export(st->hs, ref->d_kt_key, st->d_depth, slots, d_h, d_c, take, st->d_dep_n + 1);
+        skx::launch_depth_export(st->hs, ref->d_kt_key, st->stats.d_depth, slots, d_h, d_c, take, st->stats.d_dep_n + 1);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpyAsync(hashes, d_h, (size_t)take * 8, hipMemcpyDeviceToHost, st->hs);
     if (e == hipSuccess) e = hipMemcpyAsync(counts, d_c, (size_t)take * 4, hipMemcpyDeviceToHost, st->hs);
     const hipError_t e2 = hipStreamSynchronize(st->hs);
     if (e == hipSuccess) e = e2;
-    if (e != hipSuccess) rc = fail(SKX_ERR_HIP, "skx_stream_depth_export: %s", hipGetErrorString(e));
-    (void)hipFree(d_h);
-    return rc;
+    if (e != hipSuccess) return fail(SKX_ERR_HIP, "skx_stream_depth_export: %s", hipGetErrorString(e));
+    return SKX_OK;
 }
 SKX_API int skx_stream_depth_count(skx_stream* st, uint64_t* n) {
     if (!st || !n) return fail(SKX_ERR_INVALID, "NULL argument");
-    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_count: depth was never enabled on this stream");
+    if (!st->stats.d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_count: depth was never enabled on this stream");
     return depth_export_run(st, nullptr, nullptr, 0, n);
 }
 SKX_API int skx_stream_depth_export(skx_stream* st, uint64_t* hashes, uint32_t* counts, uint64_t cap, uint64_t* n) {
     if (!st || !n || (cap && (!hashes || !counts))) return fail(SKX_ERR_INVALID, "NULL argument");
-    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_export: depth was never enabled on this stream");
+    if (!st->stats.d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_export: depth was never enabled on this stream");
     return depth_export_run(st, cap ? hashes : nullptr, counts, cap, n);
 }
 SKX_API int skx_stream_depth_import(skx_stream* st, const uint64_t* hashes, const uint32_t* counts, uint64_t n, uint64_t* n_unknown) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
-    if (!st->d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_import: depth was never enabled on this stream");
+    if (!st->stats.d_depth) return fail(SKX_ERR_INVALID, "skx_stream_depth_import: depth was never enabled on this stream");
     if (n_unknown) *n_unknown = 0;
     if (n == 0) return SKX_OK;
     if (!hashes || !counts) return fail(SKX_ERR_INVALID, "NULL argument");
     const skx_ref* ref = st->ref;
     SKXCHK(use_device(st->device));
     SKXCHK(flush_pending(st));
-    u64* d_h = nullptr;
-    HIPCHK(hipMalloc(&d_h, (size_t)n * 12));
+    DevMem m;
+    HIPCHK(m.need((size_t)n * 12));
+    u64* d_h = m.as<u64>();
     u32* d_c = (u32*)(d_h + n);
     unsigned long long unknown = 0;
     hipError_t e = hipMemcpyAsync(d_h, hashes, (size_t)n * 8, hipMemcpyHostToDevice, st->hs);
     if (e == hipSuccess) e = hipMemcpyAsync(d_c, counts, (size_t)n * 4, hipMemcpyHostToDevice, st->hs);
-    if (e == hipSuccess) e = hipMemsetAsync(st->d_dep_n, 0, 8, st->hs);
+    if (e == hipSuccess) e = hipMemsetAsync(st->stats.d_dep_n, 0, 8, st->hs);
     if (e == hipSuccess) {
-        skx::launch_depth_import(st->hs, d_h, d_c, n, ref->d_kt_key, ref->kt_mask, st->d_depth, st->d_seen, st->d_dep_n);
+        skx::launch_depth_import(st->hs, d_h, d_c, n, ref->d_kt_key, ref->kt_mask, st->stats.d_depth, st->stats.d_seen, st->stats.d_dep_n);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(&unknown, st->d_dep_n, 8, hipMemcpyDeviceToHost, st->hs);
+    if (e == hipSuccess) e = hipMemcpyAsync(&unknown, st->stats.d_dep_n, 8, hipMemcpyDeviceToHost, st->hs);
     const hipError_t e2 = hipStreamSynchronize(st->hs);  // (the caller's arrays and the staging buffer are only borrowed until here)
     if (e == hipSuccess) e = e2;
-    (void)hipFree(d_h);
     if (e != hipSuccess) return fail(SKX_ERR_HIP, "skx_stream_depth_import: %s", hipGetErrorString(e));
     if (n_unknown) *n_unknown = unknown;
     return SKX_OK;
@@ -4663,20 +4651,6 @@ SKX_API int skx_sketch_reads(int device, uint32_t k, uint64_t seed, uint32_t s, 
 // records, so at most ONE group is open across a slice boundary: its partial pooled row waits in `acc` and is merged with the
 // root of the group's rows in the next slice.  Pooled rows leave in chunks of at most kPoolOutBytes.
 static const u64 kPoolRowBytes = 2ull << 30, kPoolBaseBytes = 1ull << 30, kPoolOutBytes = 256ull << 20;
-namespace {
-struct DevMem {  // a device allocation that grows on demand and is freed on every way out of the scope
-    void* p = nullptr; size_t cap = 0;
-    ~DevMem() { if (p) (void)hipFree(p); }
-    hipError_t need(size_t bytes) {
-        if (bytes <= cap && p) return hipSuccess;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        const hipError_t e = hipMalloc(&p, std::max<size_t>(bytes, 8));
-        if (e == hipSuccess) cap = bytes;
-        return e;
-    }
-    template <class T> T* as() const { return static_cast<T*>(p); }
-};
-}  // namespace
 static u32 ceil_log2(u32 n) { u32 r = 0; while (r < 32 && (1ull << r) < n) ++r; return r; }
 
 // skx_sketch_groups (counts == NULL, want_counts false: not one launch, allocation or copy more than before the counts existed)

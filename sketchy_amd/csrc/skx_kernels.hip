@@ -137,6 +137,15 @@ __global__ __launch_bounds__(256) void ref_rows_kernel(const u64* __restrict__ m
         }
     }
 }
+// the first index of exc_g (the lifted hashes, ascending by padded genome) whose genome is >= p; n_exc: none
+__device__ __forceinline__ u32 exc_first(const u32* __restrict__ exc_g, u32 n_exc, u32 p) {
+    u32 a = 0, b = n_exc;
+    while (a < b) {
+        const u32 mid = (a + b) >> 1;
+        if (exc_g[mid] < p) a = mid + 1; else b = mid;
+    }
+    return a;
+}
 // ... and what the matrix does not say by itself.  One thread per genome of the chunk: the length of its column in the matrix (entries
 // below kEmpty are a prefix: bisection), then its lifted hashes -- exc_g ascending by padded genome, a genome's hashes one after the
 // other in DESCENDING order, as skx_ref_create lists them -- appended in ascending order behind that prefix; len[i] = both together.
@@ -154,11 +163,7 @@ __global__ __launch_bounds__(256) void ref_rows_tail_kernel(const u64* __restric
         if (col[(size_t)mid * kTileGenomes] < kEmpty) lo = mid + 1; else hi = mid;
     }
     u32 n = lo;
-    u32 a = 0, b = n_exc;  // first exception of a genome >= p
-    while (a < b) {
-        const u32 mid = (a + b) >> 1;
-        if (exc_g[mid] < p) a = mid + 1; else b = mid;
-    }
+    const u32 a = exc_first(exc_g, n_exc, p);
     u32 z = a;
     while (z < n_exc && exc_g[z] == p) ++z;
     for (u32 e = z; e > a && n < row_stride; --e) rows[(size_t)i * row_stride + n++] = exc_h[e - 1];
@@ -1697,6 +1702,17 @@ __global__ void exceptions_kernel(const u32* __restrict__ exc_g, const u64* __re
 constexpr u32 kRareDense = 0xFFFFFFFFu;   // kt_off of a key held by more than R genomes: no postings, the scan finds it
 constexpr u32 kSlotNone = 0xFFFFFFFFu;    // sslot of a query hash that no genome holds (a false positive of the membership filter)
 __device__ __forceinline__ u32 kt_start(u64 key, u32 mask) { return (u32)((key ^ (key >> 29)) * 0x9E3779B1u) & mask; }
+// the slot of h in a finished key table (from `slot`, linear), or kSlotNone when h is no key: the walk ends on an empty slot, or -- a
+// full table -- after every slot
+__device__ __forceinline__ u32 kt_find(const u64* __restrict__ key, u32 mask, u64 h, u32 slot) {
+    for (u32 tries = 0;;) {
+        const u64 kk = key[slot];
+        if (kk == h) return slot;
+        if (kk == kPad || ++tries > mask) return kSlotNone;
+        slot = (slot + 1u) & mask;
+    }
+}
+__device__ __forceinline__ u32 kt_find(const u64* __restrict__ key, u32 mask, u64 h) { return kt_find(key, mask, h, kt_start(h, mask)); }
 
 // every real hash of the tiled matrix: insert its key, count the genomes that hold it (columns hold distinct hashes)
 // spmask (several species resident, or NULL): bit sp of spmask[slot] = some genome of species sp holds the key (grp_sp: species of a
@@ -4367,18 +4383,19 @@ __global__ void gather_table_kernel(const u64* __restrict__ cum, u64* __restrict
 // has left qinfo[i] = key-table slot of Q[i] (or kSlotNone: no genome holds it): one lane per distinct query hash of the pass, one
 // atomicOr per hash some genome holds (different hashes share a word; the old value is not used).  Q holds what the reads' bottom-s
 // sketches hold -- truncation came first -- and setting a bit twice changes nothing, so a pass replayed batch by batch marks the same bits.
+// Where Q[i] = h lives in a stream's per-hash state (the seen bits, the depth counters): its key-table slot, a lifted hash behind the
+// slots; kSlotNone: nowhere (no genome holds it, or the slot is out of range)
+__device__ __forceinline__ u32 stat_index(u64 h, const u32* __restrict__ qinfo, u32 i, u32 kt_slots) {
+    if (h >= kEmpty) return kt_slots + (u32)(h - kEmpty);
+    const u32 slot = qinfo[i];
+    return slot < kt_slots ? slot : kSlotNone;
+}
 __global__ __launch_bounds__(256) void seen_mark_kernel(const u64* __restrict__ q, const u32* __restrict__ n_q, u32 q_bound,
                                                         const u32* __restrict__ qinfo, u32* __restrict__ seen, u32 kt_slots) {
     const u32 nq = min(*n_q, q_bound), i = blockIdx.x * 256u + threadIdx.x;
     if (i >= nq) return;
-    const u64 h = q[i];
-    u32 bit;
-    if (h >= kEmpty) bit = kt_slots + (u32)(h - kEmpty);
-    else {
-        const u32 slot = qinfo[i];
-        if (slot == kSlotNone || slot >= kt_slots) return;
-        bit = slot;
-    }
+    const u32 bit = stat_index(q[i], qinfo, i, kt_slots);
+    if (bit == kSlotNone) return;
     const u32 m = 1u << (bit & 31u);
     if (!(seen[bit >> 5] & m)) atomicOr(&seen[bit >> 5], m);  // (most hashes of a deep sample were seen long ago: a load instead of an atomic)
 }
@@ -4392,17 +4409,30 @@ __global__ __launch_bounds__(256) void seen_mark_kernel(const u64* __restrict__ 
 // wave mostly ask for the same lines.
 // The block of rank chunk 0 also adds what the matrix does not hold: the genome's lifted hashes (exc_g ascending by padded genome, as
 // ref_rows_tail_kernel reads it) against the two lifted bits.  One atomicAdd per genome and block into covered (zero on entry).
+// The depth of a stream (below) is the same walk over one u32 counter per bit (DEPTH; state = the counters): the probes are the
+// expensive part and happen once -- per padded genome the walk adds up covered (counters > 0) and total, keeps the maximum, and leaves
+// every counter of the group in out[s + 2][64] (rank-major, lanes along the genomes: 256-byte stores; rows s and s + 1: the lifted
+// hashes; zero where the matrix holds padding or the hash was never seen) for depth_select_kernel.  covered / total / vmax [n_pad]:
+// zero on entry.  What a found index contributes is decided at compile time: the breadth walk has none of the depth walk's stores,
+// sums or LDS.
 constexpr u32 kCovRanks = 256;
-__global__ __launch_bounds__(256) void coverage_walk_kernel(const u64* __restrict__ mat, u32 s, const u32* __restrict__ groups,
-                                                            const u64* __restrict__ key, u32 mask, const u32* __restrict__ seen,
-                                                            const u32* __restrict__ exc_g, const u64* __restrict__ exc_h, u32 n_exc,
-                                                            u32* __restrict__ covered) {
-    __shared__ u32 part[4][64];
+template <bool DEPTH> __device__ __forceinline__ u32 stat_value(const u32* __restrict__ state, u32 i) {
+    if constexpr (DEPTH) return state[i];
+    else return (state[i >> 5] >> (i & 31u)) & 1u;
+}
+template <bool DEPTH>
+__device__ __forceinline__ void stat_walk(const u64* __restrict__ mat, u32 s, u32 group, const u64* __restrict__ key, u32 mask,
+                                          const u32* __restrict__ state, const u32* __restrict__ exc_g, const u64* __restrict__ exc_h,
+                                          u32 n_exc, u32* __restrict__ covered, u64* __restrict__ total, u32* __restrict__ vmax,
+                                          u32* __restrict__ out) {
+    __shared__ u32 part_n[4][64], part_m[4][64];
+    __shared__ u64 part_t[4][64];
     const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const u32 p = (groups ? groups[blockIdx.x] : blockIdx.x) * 64u + lane;  // (64 | 256: the group lies inside one tile)
+    const u32 p = group * 64u + lane;  // (64 | 256: the group lies inside one tile)
     const u64* col = mat + (size_t)(p / kTileGenomes) * s * kTileGenomes + p % kTileGenomes;
     const u32 r0 = blockIdx.y * kCovRanks, r1 = min(s, r0 + kCovRanks);
-    u32 n = 0;
+    u32 n = 0, mx = 0;
+    u64 tot = 0;
     for (u32 r = r0 + wv; r < r1; r += 16u) {
         u64 h[4];
         u32 slot[4];
@@ -4415,37 +4445,61 @@ __global__ __launch_bounds__(256) void coverage_walk_kernel(const u64* __restric
         for (u32 j = 0; j < 4u; ++j) slot[j] = kt_start(h[j], mask);
 #pragma unroll
         for (u32 j = 0; j < 4u; ++j) {
-            if (h[j] >= kEmpty) continue;
-            u32 sl = slot[j], tries = 0;
-            for (;;) {
-                const u64 kk = key[sl];
-                if (kk == h[j]) { n += (seen[sl >> 5] >> (sl & 31u)) & 1u; break; }
-                if (kk == kPad || ++tries > mask) break;  // (cannot happen: every stored hash is a key)
-                sl = (sl + 1u) & mask;
+            u32 v = 0;  // (padding, a rank beyond r1: nothing)
+            if (h[j] < kEmpty) {
+                const u32 sl = kt_find(key, mask, h[j], slot[j]);
+                if (sl != kSlotNone) v = stat_value<DEPTH>(state, sl);  // (always: every stored hash is a key)
+            }
+            if constexpr (DEPTH) {
+                const u32 rr = r + 4u * j;
+                if (rr < r1) out[(size_t)rr * 64u + lane] = v;
+                n += v != 0; tot += v; mx = max(mx, v);
+            } else n += v;
+        }
+    }
+    if (blockIdx.y == 0 && wv == 0) {
+        u32 lv[2] = {0u, 0u};  // what the genome's lifted hashes kEmpty and kEmpty + 1 contribute (a column holds a hash once)
+        for (u32 a = exc_first(exc_g, n_exc, p); a < n_exc && exc_g[a] == p; ++a) {
+            const u32 w = (u32)(exc_h[a] - kEmpty) & 1u;
+            lv[w] = stat_value<DEPTH>(state, mask + 1u + w);
+        }
+        if constexpr (DEPTH) {
+            out[(size_t)s * 64u + lane] = lv[0];
+            out[(size_t)(s + 1u) * 64u + lane] = lv[1];
+            n += (lv[0] != 0) + (lv[1] != 0); tot += (u64)lv[0] + lv[1]; mx = max(mx, max(lv[0], lv[1]));
+        } else n += lv[0] + lv[1];
+    }
+    part_n[wv][lane] = n;
+    if constexpr (DEPTH) { part_m[wv][lane] = mx; part_t[wv][lane] = tot; }
+    __syncthreads();
+    if (wv == 0) {
+        const u32 tn = part_n[0][lane] + part_n[1][lane] + part_n[2][lane] + part_n[3][lane];
+        if (tn) {
+            atomicAdd(&covered[p], tn);
+            if constexpr (DEPTH) {
+                atomicAdd(&total[p], part_t[0][lane] + part_t[1][lane] + part_t[2][lane] + part_t[3][lane]);
+                atomicMax(&vmax[p], max(max(part_m[0][lane], part_m[1][lane]), max(part_m[2][lane], part_m[3][lane])));
             }
         }
     }
-    if (blockIdx.y == 0 && wv == 0 && n_exc) {
-        u32 a = 0, b = n_exc;  // first exception of a genome >= p
-        while (a < b) {
-            const u32 mid = (a + b) >> 1;
-            if (exc_g[mid] < p) a = mid + 1; else b = mid;
-        }
-        const u32 lifted = seen[(mask + 1u) >> 5] >> ((mask + 1u) & 31u);  // (the table has a power of two of slots, at least 32: both bits in one word)
-        for (; a < n_exc && exc_g[a] == p; ++a) n += (lifted >> (u32)(exc_h[a] - kEmpty)) & 1u;
-    }
-    part[wv][lane] = n;
-    __syncthreads();
-    if (wv == 0) {
-        const u32 t = part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
-        if (t) atomicAdd(&covered[p], t);
-    }
 }
-// the padded counts as the caller sees them: out[i] = covered[real2pad[genomes ? genomes[i] : i]]
-__global__ void coverage_gather_kernel(const u32* __restrict__ covered, const u32* __restrict__ real2pad, const u32* __restrict__ genomes, u32 n,
-                                       u32* __restrict__ out) {
+__global__ __launch_bounds__(256) void coverage_walk_kernel(const u64* __restrict__ mat, u32 s, const u32* __restrict__ groups,
+                                                            const u64* __restrict__ key, u32 mask, const u32* __restrict__ seen,
+                                                            const u32* __restrict__ exc_g, const u64* __restrict__ exc_h, u32 n_exc,
+                                                            u32* __restrict__ covered) {
+    stat_walk<false>(mat, s, groups ? groups[blockIdx.x] : blockIdx.x, key, mask, seen, exc_g, exc_h, n_exc, covered, nullptr, nullptr, nullptr);
+}
+// the per-genome results (padded order) as the caller sees them: out_x[i] = x[real2pad[genomes ? genomes[i] : i]]; an output that is
+// NULL is not wanted (and its input is not read)
+__global__ void genome_gather_kernel(const u32* __restrict__ covered, const u32* __restrict__ median, const u64* __restrict__ total,
+                                     const u32* __restrict__ real2pad, const u32* __restrict__ genomes, u32 n, u32* __restrict__ out_cov,
+                                     u32* __restrict__ out_med, u64* __restrict__ out_tot) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = covered[real2pad[genomes ? genomes[i] : i]];
+    if (i >= n) return;
+    const u32 p = real2pad[genomes ? genomes[i] : i];
+    if (out_cov) out_cov[i] = covered[p];
+    if (out_med) out_med[i] = median[p];
+    if (out_tot) out_tot[i] = total[p];
 }
 // ... and widened for rank_table_kernel, which ranks a padded u64 table in (value desc, index asc) order
 __global__ void coverage_widen_kernel(const u32* __restrict__ covered, u32 n_pad, u64* __restrict__ wide) {
@@ -4495,89 +4549,17 @@ __global__ __launch_bounds__(256) void depth_apply_kernel(const u64* __restrict_
     const u32 c = tmp[i];
     if (!c) return;
     tmp[i] = 0;
-    const u64 h = q[i];
-    u32 at;
-    if (h >= kEmpty) at = kt_slots + (u32)(h - kEmpty);
-    else {
-        at = qinfo[i];
-        if (at == kSlotNone || at >= kt_slots) return;
-    }
-    depth[at] = sat_add_u32(depth[at], c);
+    const u32 at = stat_index(q[i], qinfo, i, kt_slots);
+    if (at != kSlotNone) depth[at] = sat_add_u32(depth[at], c);
 }
-// The query side, part 1: coverage_walk_kernel's walk (same unit, same lanes, four dependent probes in flight, the lifted hashes from
-// exc_g / exc_h in the block of rank chunk 0), reading the counter where that reads the bit.  The probes are the expensive part and happen
-// once: per padded genome the walk adds up covered (counters > 0) and total, keeps the maximum, and leaves every counter of the group in
-// vals[group of the launch][s + 2][64] (rank-major, lanes along the genomes: 256-byte stores; rows s and s + 1: the lifted hashes; zero where
-// the matrix holds padding or the hash was never seen) for the select below.  covered / total / vmax [n_pad]: zero on entry.
+// The query side, part 1: stat_walk over the counters (above), the groups of one launch side by side in vals
 __global__ __launch_bounds__(256) void depth_walk_kernel(const u64* __restrict__ mat, u32 s, const u32* __restrict__ groups, u32 g0,
                                                          const u64* __restrict__ key, u32 mask, const u32* __restrict__ depth,
                                                          const u32* __restrict__ exc_g, const u64* __restrict__ exc_h, u32 n_exc,
                                                          u32* __restrict__ covered, u64* __restrict__ total, u32* __restrict__ vmax,
                                                          u32* __restrict__ vals) {
-    __shared__ u32 part_n[4][64], part_m[4][64];
-    __shared__ u64 part_t[4][64];
-    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    const u32 p = (groups ? groups[blockIdx.x] : g0 + blockIdx.x) * 64u + lane;  // (64 | 256: the group lies inside one tile)
-    const u64* col = mat + (size_t)(p / kTileGenomes) * s * kTileGenomes + p % kTileGenomes;
-    u32* out = vals + (size_t)blockIdx.x * (s + 2u) * 64u + lane;
-    const u32 r0 = blockIdx.y * kCovRanks, r1 = min(s, r0 + kCovRanks);
-    u32 n = 0, mx = 0;
-    u64 tot = 0;
-    for (u32 r = r0 + wv; r < r1; r += 16u) {
-        u64 h[4];
-        u32 slot[4];
-#pragma unroll
-        for (u32 j = 0; j < 4u; ++j) {
-            const u32 rr = r + 4u * j;
-            h[j] = rr < r1 ? col[(size_t)rr * kTileGenomes] : kPad;
-        }
-#pragma unroll
-        for (u32 j = 0; j < 4u; ++j) slot[j] = kt_start(h[j], mask);
-#pragma unroll
-        for (u32 j = 0; j < 4u; ++j) {
-            const u32 rr = r + 4u * j;
-            if (rr >= r1) continue;
-            u32 v = 0;
-            if (h[j] < kEmpty) {
-                u32 sl = slot[j], tries = 0;
-                for (;;) {
-                    const u64 kk = key[sl];
-                    if (kk == h[j]) { v = depth[sl]; break; }
-                    if (kk == kPad || ++tries > mask) break;  // (cannot happen: every stored hash is a key)
-                    sl = (sl + 1u) & mask;
-                }
-            }
-            out[(size_t)rr * 64u] = v;
-            n += v != 0; tot += v; mx = max(mx, v);
-        }
-    }
-    if (blockIdx.y == 0 && wv == 0) {
-        u32 lv[2] = {0u, 0u};
-        if (n_exc) {
-            u32 a = 0, b = n_exc;  // first exception of a genome >= p
-            while (a < b) {
-                const u32 mid = (a + b) >> 1;
-                if (exc_g[mid] < p) a = mid + 1; else b = mid;
-            }
-            for (; a < n_exc && exc_g[a] == p; ++a) {
-                const u32 w = (u32)(exc_h[a] - kEmpty) & 1u;
-                lv[w] = depth[(size_t)mask + 1u + w];
-            }
-        }
-        out[(size_t)s * 64u] = lv[0];
-        out[(size_t)(s + 1u) * 64u] = lv[1];
-        n += (lv[0] != 0) + (lv[1] != 0); tot += (u64)lv[0] + lv[1]; mx = max(mx, max(lv[0], lv[1]));
-    }
-    part_n[wv][lane] = n; part_m[wv][lane] = mx; part_t[wv][lane] = tot;
-    __syncthreads();
-    if (wv == 0) {
-        const u32 tn = part_n[0][lane] + part_n[1][lane] + part_n[2][lane] + part_n[3][lane];
-        if (tn) {
-            atomicAdd(&covered[p], tn);
-            atomicAdd(&total[p], part_t[0][lane] + part_t[1][lane] + part_t[2][lane] + part_t[3][lane]);
-            atomicMax(&vmax[p], max(max(part_m[0][lane], part_m[1][lane]), max(part_m[2][lane], part_m[3][lane])));
-        }
-    }
+    stat_walk<true>(mat, s, groups ? groups[blockIdx.x] : g0 + blockIdx.x, key, mask, depth, exc_g, exc_h, n_exc, covered, total, vmax,
+                    vals + (size_t)blockIdx.x * (s + 2u) * 64u);
 }
 // Part 2: the lower median of a genome's covered counters = the element of rank (covered - 1) / 2 of the non-zero values of its column of
 // vals, ascending.  One workgroup per group of the launch, an MSB-first radix select: per byte round the four waves read the group's rows
@@ -4622,15 +4604,6 @@ __global__ __launch_bounds__(256) void depth_select_kernel(const u32* __restrict
     }
     if (wv == 0) median[p] = cov ? pre[lane] : 0u;
 }
-// out[i] of the three results for padded genome real2pad[genomes ? genomes[i] : i]; an output that is NULL is not wanted
-__global__ void depth_gather_kernel(const u32* __restrict__ covered, const u32* __restrict__ median, const u64* __restrict__ total,
-                                    const u32* __restrict__ real2pad, const u32* __restrict__ genomes, u32 n, u32* __restrict__ out_cov,
-                                    u32* __restrict__ out_med, u64* __restrict__ out_tot) {
-    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const u32 p = real2pad[genomes ? genomes[i] : i];
-    out_cov[i] = covered[p]; out_med[i] = median[p]; out_tot[i] = total[p];
-}
 // Portable state: the counters by HASH (the key table is filled by atomic insertion: its slot layout differs between two builds of one
 // reference).  depth_export_kernel: every index with a counter > 0 -> (key[slot] or the lifted value, counter) at the next free place;
 // *n counts them all, the arrays take the first cap (hashes == NULL: count only).
@@ -4665,13 +4638,8 @@ __global__ __launch_bounds__(256) void depth_import_kernel(const u64* __restrict
     u64 at;
     if (h >= kEmpty) at = (u64)mask + 1u + (h - kEmpty);
     else {
-        u32 sl = kt_start(h, mask), tries = 0;
-        for (;;) {
-            const u64 kk = key[sl];
-            if (kk == h) break;
-            if (kk == kPad || ++tries > mask) { atomicAdd(n_unknown, 1ull); return; }
-            sl = (sl + 1u) & mask;
-        }
+        const u32 sl = kt_find(key, mask, h);
+        if (sl == kSlotNone) { atomicAdd(n_unknown, 1ull); return; }
         at = sl;
     }
     if (!c) return;
@@ -6468,9 +6436,11 @@ void launch_coverage_walk(hipStream_t st, const u64* mat, u32 s, const u32* grou
     hipLaunchKernelGGL(coverage_walk_kernel, dim3(n_groups, cdiv(s, kCovRanks)), dim3(256), 0, st, mat, s, groups, key, mask, seen, exc_g, exc_h,
                        n_exc, covered);
 }
-void launch_coverage_gather(hipStream_t st, const u32* covered, const u32* real2pad, const u32* genomes, u32 n, u32* out) {
+void launch_genome_gather(hipStream_t st, const u32* covered, const u32* median, const u64* total, const u32* real2pad, const u32* genomes,
+                          u32 n, u32* out_cov, u32* out_med, u64* out_tot) {
     if (n == 0) return;
-    hipLaunchKernelGGL(coverage_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, covered, real2pad, genomes, n, out);
+    hipLaunchKernelGGL(genome_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, covered, median, total, real2pad, genomes, n, out_cov,
+                       out_med, out_tot);
 }
 void launch_coverage_widen(hipStream_t st, const u32* covered, u32 n_pad, u64* wide) {
     hipLaunchKernelGGL(coverage_widen_kernel, dim3(cdiv(n_pad, 256)), dim3(256), 0, st, covered, n_pad, wide);
@@ -6489,12 +6459,6 @@ void launch_depth_walk(hipStream_t st, const u64* mat, u32 s, const u32* groups,
     hipLaunchKernelGGL(depth_walk_kernel, dim3(n_groups, cdiv(s, kCovRanks)), dim3(256), 0, st, mat, s, groups, g0, key, mask, depth, exc_g,
                        exc_h, n_exc, covered, total, vmax, vals);
     hipLaunchKernelGGL(depth_select_kernel, dim3(n_groups), dim3(256), 0, st, vals, s, groups, g0, covered, vmax, median);
-}
-void launch_depth_gather(hipStream_t st, const u32* covered, const u32* median, const u64* total, const u32* real2pad, const u32* genomes,
-                         u32 n, u32* out_cov, u32* out_med, u64* out_tot) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(depth_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, covered, median, total, real2pad, genomes, n, out_cov,
-                       out_med, out_tot);
 }
 void launch_depth_export(hipStream_t st, const u64* key, const u32* depth, u64 kt_slots, u64* hashes, u32* counts, u64 cap,
                          unsigned long long* n) {

@@ -404,8 +404,10 @@ void launch_seen_mark(hipStream_t st, const u64* q, const u32* n_q, u32 q_bound,
 // 0 .. n_groups - 1, the whole table); covered [n_pad], zero on entry for those genomes
 void launch_coverage_walk(hipStream_t st, const u64* mat, u32 s, const u32* groups, u32 n_groups, const u64* key, u32 mask, const u32* seen,
                           const u32* exc_g, const u64* exc_h, u32 n_exc, u32* covered);
-// out[i] = covered[real2pad[genomes ? genomes[i] : i]], i < n;  wide[p] = covered[p], p < n_pad (for launch_rank_table)
-void launch_coverage_gather(hipStream_t st, const u32* covered, const u32* real2pad, const u32* genomes, u32 n, u32* out);
+// out_x[i] = x[real2pad[genomes ? genomes[i] : i]], i < n, for the per-genome results of the breadth and depth walks; an output that is
+// NULL is not wanted.  wide[p] = covered[p], p < n_pad (for launch_rank_table)
+void launch_genome_gather(hipStream_t st, const u32* covered, const u32* median, const u64* total, const u32* real2pad, const u32* genomes,
+                          u32 n, u32* out_cov, u32* out_med, u64* out_tot);
 void launch_coverage_widen(hipStream_t st, const u32* covered, u32 n_pad, u64* wide);
 // ---- depth of a stream (skx_kernels.hip, "depth of a stream").  depth: one u32 per bit of `seen`, same indices, saturating.
 // launch_depth_mark: behind launch_pair_q of the same pass, same stream (pair_h, q, n_q, bbase, btot: its; qinfo: its launch_classify's);
@@ -419,8 +421,6 @@ inline size_t depth_vals_per_group(u32 s) { return ((size_t)s + 2u) * 64u; }
 void launch_depth_walk(hipStream_t st, const u64* mat, u32 s, const u32* groups, u32 g0, u32 n_groups, const u64* key, u32 mask,
                        const u32* depth, const u32* exc_g, const u64* exc_h, u32 n_exc, u32* covered, u64* total, u32* vmax, u32* median,
                        u32* vals);
-void launch_depth_gather(hipStream_t st, const u32* covered, const u32* median, const u64* total, const u32* real2pad, const u32* genomes,
-                         u32 n, u32* out_cov, u32* out_med, u64* out_tot);
 // *n += indices with a counter > 0 (zero on entry); hashes / counts [cap] take the first cap of them (hashes == NULL: count only)
 void launch_depth_export(hipStream_t st, const u64* key, const u32* depth, u64 kt_slots, u64* hashes, u32* counts, u64 cap,
                          unsigned long long* n);

@@ -426,6 +426,51 @@ def test_state(gpu):
         R.close()
 
 
+def test_interleaved_queries_on_one_stream(gpu):
+    """the breadth and depth queries and the two rankings share their list and ranking scratch: long and short lists, whole tables and
+    rankings of one and five rows alternate on ONE stream after the 1 200 reads, every answer against the oracle's"""
+    d, refs, col_lens, bases, offsets = cc.single(64)
+    exp = dc.single_expected(64)[1200]
+    cov = cc.single_expected(64, None)[1200]
+    cum = _oracle_table(64, 48, 1200)["cum"]
+    by_sum = np.lexsort((np.arange(1300), -cum.astype(np.int64)))
+    long_list = np.concatenate([np.arange(1300, dtype=np.uint32)[::-1], np.arange(0, 1300, 130, dtype=np.uint32)])
+    perm = ((np.arange(1300, dtype=np.int64) * 577 + 13) % 1300).astype(np.uint32)   # (577 and 1300 are coprime)
+    assert len(long_list) == 1310 and len(set(perm.tolist())) == 1300
+    R, _, _ = cc.create_reference(d, R_, s=cc.S_SINGLE)
+    try:
+        S = _stream(R, bases, top=1)
+        try:
+            S.enable_depth()
+            S.push(bases, offsets)
+
+            def check_rank(top):
+                idx, sm = S.rank(top)
+                np.testing.assert_array_equal(idx, by_sum[:top], err_msg=f"rank({top}) idx")
+                np.testing.assert_array_equal(sm, cum[by_sum[:top]], err_msg=f"rank({top}) sum")
+
+            def check_coverage_rank(top):
+                idx, val = cc.expected_rank(cov, [1300], top)
+                gi, gv = S.coverage_rank(top)
+                np.testing.assert_array_equal(gi, idx, err_msg=f"coverage_rank({top}) idx")
+                np.testing.assert_array_equal(gv, val, err_msg=f"coverage_rank({top}) covered")
+            np.testing.assert_array_equal(S.coverage_rows(long_list), cov[long_list], err_msg="1 coverage_rows, 1310 entries")
+            _assert_depth(S.depth_rows([1299]), [e[[1299]] for e in exp], "2 depth_rows([1299])")
+            np.testing.assert_array_equal(S.coverage_rows(cc.ROWS_1300), cov[cc.ROWS_1300], err_msg="3 coverage_rows(ROWS_1300)")
+            _assert_depth(S.depth_rows(perm), [e[perm] for e in exp], "4 depth_rows, a permutation of all")
+            check_coverage_rank(1)
+            check_rank(5)
+            check_coverage_rank(5)
+            check_rank(1)
+            _assert_depth(S.depth(), exp, "9 depth()")
+            np.testing.assert_array_equal(S.coverage(), cov, err_msg="10 coverage()")
+            np.testing.assert_array_equal(exp[0], cov)
+        finally:
+            S.close()
+    finally:
+        R.close()
+
+
 def _screen_lines(names, col_len, exp, table, top, depth=False, identity=False, geno=None):
     cov, med = exp[0], exp[1]
     size = col_len.astype(np.int64)

@@ -1136,6 +1136,12 @@ struct skx_stream {
     u64 *d_cw = nullptr;
     u64 *d_inb = nullptr, *d_hit = nullptr;  // [kPassBatchesMax][ref->n_lw]: the bit rows on a batch's list / those that hold a candidate of it
     skx::LongRows long_rows() const { return skx::LongRows{d_lrow, d_nlrow, qcap + 128, d_inb, ref->n_lw}; }
+    // the counts of a pass's dense rows (then its patterns) as the int8 operand of the gains' matrix product: skx::GainOperand, one
+    // scratch for both calls of a pass (same stream, one after the other)
+    void *d_gop = nullptr;
+    u32 *d_gop_pairs = nullptr, gop_words = 0;
+    u32 gop_words_for(u32 rows) const { return std::max(std::max(rows / 64 + 2, (ref->n_sd + 63u) / 64u), npat_pad / 64); }
+    skx::GainOperand gain_operand() const { return skx::GainOperand{d_gop, d_gop_pairs, gop_words}; }
     // rows whose list is a pattern + exceptions (references with patterns; a stream whose compact problems are wider than the pattern
     // kernels' LDS rows -- more than eight species -- does without: its dictionaries never flag a row)
     bool use_pat = false;
@@ -1399,7 +1405,7 @@ static void stream_free(skx_stream* st) {
                     st->d_topk_idx, st->d_topk_sum, st->d_cons, st->d_ev.n_events, st->d_ev.ev_read, st->d_ev.ev_idx, st->d_ev.ev_sum, st->d_ev.ev_codes, st->d_tab_tmp, st->d_rank_idx, st->d_rank_sum, st->d_bsum, st->d_grp_any[0],
                     st->d_grp_any[1], st->d_hbuf, st->d_wb[0], st->d_wb[1], st->d_rowany[0], st->d_rowany[1], st->d_mqext,
                     st->d_qd, st->d_qrow, st->d_sslot, st->d_qinfo, st->d_qloc, st->d_cls_bsum, st->d_nd_hs,
-                    st->d_rowcnt, st->d_gain, st->d_gain_s, st->d_candslot, st->d_candmask, st->d_lrow, st->d_nlrow, st->d_gain_l, st->d_cbase, st->d_cwl, st->d_ncwl, st->d_cw, st->d_cbad, st->d_nqc, st->d_spc_g0, st->d_spc_grp, st->d_inb, st->d_hit, st->d_hist, st->d_nprow, st->d_pcw, st->d_ms[0], st->d_ms[1], st->d_mdirty_s};
+                    st->d_rowcnt, st->d_gain, st->d_gain_s, st->d_candslot, st->d_candmask, st->d_lrow, st->d_gop, st->d_gop_pairs, st->d_nlrow, st->d_gain_l, st->d_cbase, st->d_cwl, st->d_ncwl, st->d_cw, st->d_cbad, st->d_nqc, st->d_spc_g0, st->d_spc_grp, st->d_inb, st->d_hit, st->d_hist, st->d_nprow, st->d_pcw, st->d_ms[0], st->d_ms[1], st->d_mdirty_s};
     for (auto& q : st->ps) {
         for (void* x : {(void*)q.tab, (void*)q.cand, (void*)q.tabc, (void*)q.ncand, (void*)q.mode, (void*)q.any_full, (void*)q.nqc_total, (void*)q.mc, (void*)q.mqc,
                         (void*)q.rowany_c, (void*)q.grp_any_c, (void*)q.smap, (void*)q.pair_qc, (void*)q.nd}) (void)hipFree(x);
@@ -1916,6 +1922,9 @@ static int stream_create_internal(skx_stream** out, const skx_ref* ref, u32 top_
                 SCHK(hipMalloc(&st->d_pcw, (size_t)nb * ref->n_pat * st->n_grp_c * skx::kRankWords * 8));
             }
         }
+        st->gop_words = st->gop_words_for(st->qcap);  // (npat_pad is known here)
+        SCHK(hipMalloc(&st->d_gop, skx::gain_operand_bytes(st->gop_words)));
+        SCHK(hipMalloc(&st->d_gop_pairs, (size_t)st->gop_words * 4));
         SCHK(hipMalloc(&st->d_cbad, 64));
         SCHK(hipMalloc(&st->d_nqc, skx::pass_counter_bytes()));
         std::vector<u32> g0c(n_sp), grpc(st->n_grp_c);
@@ -2070,7 +2079,10 @@ static int grow_query_rows(skx_stream* st, u64 want_rows) {
     u64 *m = nullptr, *mint = nullptr, *mq[2] = {nullptr, nullptr}, *ra[2] = {nullptr, nullptr};
     u32 *wb[2] = {nullptr, nullptr}, *cnt = nullptr, *sm[2] = {nullptr, nullptr};
     uint2* lrow = nullptr;
-    auto undo = [&]() { for (void* q : {(void*)m, (void*)mint, (void*)mq[0], (void*)mq[1], (void*)ra[0], (void*)ra[1], (void*)wb[0], (void*)wb[1], (void*)cnt, (void*)sm[0], (void*)sm[1], (void*)lrow}) if (q) (void)hipFree(q); (void)hipGetLastError(); };
+    void* gop = nullptr;
+    u32* gop_pairs = nullptr;
+    const u32 gop_words = st->gop_words_for((u32)rows);
+    auto undo = [&]() { for (void* q : {(void*)m, (void*)mint, (void*)mq[0], (void*)mq[1], (void*)ra[0], (void*)ra[1], (void*)wb[0], (void*)wb[1], (void*)cnt, (void*)sm[0], (void*)sm[1], (void*)lrow, gop, (void*)gop_pairs}) if (q) (void)hipFree(q); (void)hipGetLastError(); };
     hipError_t e = st->static_dense ? hipSuccess : hipMalloc(&m, (size_t)(rows / 64 + 2) * n_pad * 8);  // (static dense rows: M does not grow)
     if (e == hipSuccess && st->d_mint) e = hipMalloc(&mint, (size_t)(rows / 64 + 2) * n_pad * 8);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc(&mq[i], ((size_t)rows + 128) * mq_words * 8);
@@ -2078,6 +2090,8 @@ static int grow_query_rows(skx_stream* st, u64 want_rows) {
     for (int i = 0; i < 2 && e == hipSuccess && st->d_wb[i]; ++i) e = hipMalloc(&wb[i], ((size_t)rows / 64 + 1) * ref->n_tiles * 16);
     if (e == hipSuccess) e = hipMalloc(&cnt, (size_t)skx::kPassBatchesMax * ((size_t)rows + 128) * 4);
     if (e == hipSuccess && st->d_lrow) e = hipMalloc(&lrow, (size_t)skx::kPassBatchesMax * ((size_t)rows + 128) * 8);
+    if (e == hipSuccess && gop_words > st->gop_words) e = hipMalloc(&gop, skx::gain_operand_bytes(gop_words));
+    if (e == hipSuccess && gop_words > st->gop_words) e = hipMalloc(&gop_pairs, (size_t)gop_words * 4);
     for (int i = 0; i < 2 && e == hipSuccess; ++i) e = hipMalloc(&sm[i], (size_t)skx::kPassBatchesMax * ((size_t)rows + 128) * 4);
     if (e == hipSuccess && m) e = hipMemset(m, 0, (size_t)(rows / 64 + 2) * n_pad * 8);  // (M is all-zero between passes)
     // (the group-major matrices and their row flags start all-zero: clean under any row stride -- d_mqext below)
@@ -2102,6 +2116,7 @@ static int grow_query_rows(skx_stream* st, u64 want_rows) {
     st->rowcnt_ext.whole();  // (fresh allocations are not zero: the next use of every slot clears all of it)
     for (auto& q : st->ps) q.smap_ext.whole();
     if (lrow) { (void)hipFree(st->d_lrow); st->d_lrow = lrow; }
+    if (gop && gop_pairs) { (void)hipFree(st->d_gop); (void)hipFree(st->d_gop_pairs); st->d_gop = gop; st->d_gop_pairs = gop_pairs; st->gop_words = gop_words; }
     st->qcap = (u32)rows;
     st->mq_stride[0] = st->mq_stride[1] = 0;
     st->qrows_grown += 1;
@@ -2347,12 +2362,13 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
         const skx::RareIndex ri = st->rare_index();
         const skx::LongRows lrows = st->long_rows();
         const skx::PatRows prows = st->pat_rows();
+        const skx::GainOperand gop = st->gain_operand();
         skx::launch_gain_sparse(on, d_nd, q_bound, st->d_rowcnt, qstride, (u32)n_sub, n_pad, st->d_gain_s, st->d_sslot, ri, long_rows ? &lrows : nullptr, walk_scale,
                                 (long_rows && st->use_pat) ? &prows : nullptr);
         if (long_rows) skx::launch_gain_long(on, lrows, ri, d_nd, st->d_rowcnt, qstride, (u32)n_sub, n_pad, st->d_gain_l, walk_scale);
         // the pattern rows' part: gain_l[b][g] += sum over the patterns of hist[b][p] x PM[p][g] -- the dense rows' kernel on the pattern matrix
         if (long_rows && st->use_pat)
-            skx::launch_gain_dense(on, ri.pm, nullptr, n_pad, ri.d_npat, ri.n_pat, st->d_hist, st->npat_pad, (u32)n_sub, st->d_gain_l);
+            skx::launch_gain_dense(on, ri.pm, nullptr, n_pad, ri.d_npat, ri.n_pat, st->d_hist, st->npat_pad, (u32)n_sub, st->d_gain_l, nullptr, nullptr, &gop);
         HIPCHK(hipGetLastError());
         return SKX_OK;
     };
@@ -2489,8 +2505,9 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
         }
         if (P > 0) {
             SKXCHK(row_counts());
+            const skx::GainOperand gop = st->gain_operand();
             skx::launch_gain_dense(hs, d_m, m_int, n_pad, d_nd, sdm ? ref->n_sd : q_bound, st->d_rowcnt, qstride, (u32)n_sub, st->d_gain,
-                                   (sdm && ref->n_species > 1) ? ref->d_segw : nullptr, ref->d_grp_sp);
+                                   (sdm && ref->n_species > 1) ? ref->d_segw : nullptr, ref->d_grp_sp, &gop);
             if (split_dict) SKXCHK(rare_gains(hs));
         }
         skx::launch_pass_tables(hs, st->d_cum, st->d_gain, (split_dict && P > 0) ? st->d_gain_s : nullptr,
@@ -5390,8 +5407,12 @@ SKX_API void skx_comm_destroy(skx_comm* comm) {
 
 #ifdef SKX_EXPERIMENTS
 namespace skx { void rank_debug_counters(unsigned long long* out, bool reset); }
+namespace skx { void gain_dense_launches(unsigned long long* out, bool reset); }
 // experiments build only: counters of rank_seg_top1_kernel (see skx_kernels.hip); out[128]
 SKX_API void skx_debug_rank_counters(unsigned long long* out, int reset) { skx::rank_debug_counters(out, reset != 0); }
+// experiments build only: launches of the dense rows' gains since the last reset -- out[0] as the int8 matrix product, out[1] by the
+// bit-by-bit kernel (tests: which of the two a stream's passes really took)
+SKX_API void skx_debug_gain_launches(unsigned long long* out, int reset) { skx::gain_dense_launches(out, reset != 0); }
 // experiments build only: row_topk_kernel alone on a caller's counts [n_rows][n] (one species of n genomes, padded to whole rank groups
 // here): what skx_rank_sketches cannot reach at test sizes -- bounds of three and four significant bytes.  top_idx / top_val [n_rows][top_k]
 SKX_API int skx_debug_row_topk(int device, const uint32_t* counts, uint32_t n_rows, uint32_t n, uint32_t top_k, uint32_t bound,

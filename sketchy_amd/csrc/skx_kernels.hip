@@ -23,6 +23,7 @@
 //
 // Integer work throughout (u64 hash compares, bit counts): no MFMA.
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <mutex>
 #include <type_traits>
@@ -4724,6 +4725,111 @@ __global__ __launch_bounds__(256) void gain_dense_kernel(const u64* __restrict__
     for (u32 b = 0; b < NB; ++b)
         if (acc[b]) atomicAdd(&gain[(size_t)b * n_pad + g], acc[b]);
 }
+// The same sum as an int8 matrix product (v_mfma_i32_16x16x64_i8): the 64 rows of a query word are the summed dimension.
+//   A = 16 genomes x 64 rows: lane l holds genome l & 15 of the fragment and rows 16 (l >> 4) .. + 15 of the word -- its 16 bits of
+//       m_bits[w][g], four bits to four bytes of 0 / 1 by ((x & 0xF) * 0x00204081) & 0x01010101 (the shifted copies x, x << 7, x << 14,
+//       x << 21 meet in no bit: no carries; byte t = bit t);
+//   B = 64 rows x 16 columns, column = (batch, 7-bit plane of its count): MFMA int8 is SIGNED, so a count goes in as planes of 0 .. 127.
+//       Columns 0 - 7 = plane 0 of batches 0 - 7, columns 8 - 15 = plane 1: counts below 2^14; a second operand with planes 2 and 3
+//       (counts below 2^28; a batch has at most 2^22 pairs) is issued only for the words that hold such a count.
+// gain_operand_kernel writes B once per call in fragment order -- lane l: column l & 15, rows 16 (l >> 4) + j in byte j, the SAME
+// row-to-(lane, byte) map as A's, which is all the product needs: it sums over the rows -- with the plane pairs every word needs;
+// the gain waves load it with one 16-byte load per lane.  No scalar count loads, no v_bfe / v_mad per (row, genome).
+// Accumulators are int32 per plane: rows x 127 < 2^31 for every row capacity the library allows (2^22 rows: 2^29); the planes are
+// put together as lo + 128 hi (+ 2^14 x the second pair's) in u32, which is exact for the true sums (below 2^32 like the old kernel's).
+using v4i = __attribute__((ext_vector_type(4))) int;
+constexpr u32 kGopLaneBytes = 16;                       // a lane's part of a B fragment
+constexpr u32 kGopWordBytes = 64u * kGopLaneBytes;      // one word's fragment of one plane pair
+__global__ __launch_bounds__(256) void gain_operand_kernel(const u32* __restrict__ n_d, const u32* __restrict__ cnt, u32 row_stride, u32 n_b,
+                                                           v4i* __restrict__ frag, u32* __restrict__ pairs, u32 words_cap) {
+    __builtin_amdgcn_s_setprio(3);
+    const u32 lane = lane_id(), w = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const u32 nd = n_d[0], n_words = min((nd + 63u) >> 6, words_cap);
+    if (w >= n_words) return;
+    const u32 b = lane & 7u, hi = (lane >> 3) & 1u, r0 = w * 64u + (lane >> 4) * 16u;
+    u32 lo4[4], hi4[4], big = 0;
+#pragma unroll
+    for (u32 d = 0; d < 4u; ++d) {
+        lo4[d] = 0; hi4[d] = 0;
+#pragma unroll
+        for (u32 t = 0; t < 4u; ++t) {
+            const u32 r = r0 + d * 4u + t;
+            const u32 c = (b < n_b && r < nd) ? cnt[(size_t)b * row_stride + r] : 0u;
+            big |= c >> 14;
+            lo4[d] |= ((c >> (7u * hi)) & 127u) << (8u * t);
+            hi4[d] |= ((c >> (14u + 7u * hi)) & 127u) << (8u * t);
+        }
+    }
+    const bool two = __ballot(big != 0u) != 0ull;
+    frag[(size_t)w * 64u + lane] = v4i{(int)lo4[0], (int)lo4[1], (int)lo4[2], (int)lo4[3]};
+    if (two) frag[((size_t)words_cap + w) * 64u + lane] = v4i{(int)hi4[0], (int)hi4[1], (int)hi4[2], (int)hi4[3]};
+    if (lane == 0u) pairs[w] = two ? 2u : 1u;
+}
+__device__ __forceinline__ v4i bits16_to_bytes(u32 x) {
+    v4i a;
+    a.x = (int)((((x >> 0) & 0xFu) * 0x00204081u) & 0x01010101u);
+    a.y = (int)((((x >> 4) & 0xFu) * 0x00204081u) & 0x01010101u);
+    a.z = (int)((((x >> 8) & 0xFu) * 0x00204081u) & 0x01010101u);
+    a.w = (int)((((x >> 12) & 0xFu) * 0x00204081u) & 0x01010101u);
+    return a;
+}
+// grid: n_pad / 64 workgroups of four waves: a workgroup owns 64 genomes (four A fragments per word) and ALL the words of its species,
+// split over its waves word by word; the waves' sums meet in LDS and leave as plain read-add-stores: no atomics.
+// C / D map of the 16x16 shapes: lane l, register r = row 4 (l >> 4) + r (genome of the fragment), column l & 15.
+__global__ __launch_bounds__(256) void gain_dense_mfma_kernel(const u64* __restrict__ m_bits, u32 n_pad, const u32* __restrict__ n_d,
+                                                              const v4i* __restrict__ frag, const u32* __restrict__ pairs, u32 words_cap,
+                                                              u32 words_written, u32 n_b, u32* __restrict__ gain, const u32* __restrict__ segw,
+                                                              const u32* __restrict__ grp_sp) {
+    __builtin_amdgcn_s_setprio(2);
+    __shared__ u32 red[4][kPassBatchesMax][64];
+    const u32 lane = lane_id(), wv = threadIdx.x >> 6, g0 = blockIdx.x * 64u;
+    const u32 nd = n_d[0];
+    // (words_written: the words gain_operand_kernel's grid covered -- nothing beyond them is read, whatever n_d says)
+    u32 w0 = 0, w1 = min(min((nd + 63u) >> 6, words_cap), words_written);
+    if (segw) {
+        const u32 sp = grp_sp[blockIdx.x / kRankWords];
+        w0 = max(w0, segw[2u * sp]); w1 = min(w1, segw[2u * sp + 1u]);
+    }
+    if (w0 >= w1) return;  // (uniform over the workgroup)
+    const unsigned short* ms = reinterpret_cast<const unsigned short*>(m_bits);  // (little-endian: quarter q of a word = its bits 16 q .. 16 q + 15)
+    const u32 gi = lane & 15u, q = lane >> 4;
+    v4i acc[4], acc2[4];
+#pragma unroll
+    for (u32 f = 0; f < 4u; ++f) { acc[f] = v4i{0, 0, 0, 0}; acc2[f] = v4i{0, 0, 0, 0}; }
+    for (u32 w = w0 + wv; w < w1; w += 4u) {
+        u32 a[4];
+#pragma unroll
+        for (u32 f = 0; f < 4u; ++f) a[f] = ms[((size_t)w * n_pad + g0 + 16u * f + gi) * 4u + q];
+        if (__ballot((a[0] | a[1] | a[2] | a[3]) != 0u) == 0ull) continue;
+        const v4i b0 = frag[(size_t)w * 64u + lane];
+        const u32 np = (u32)__builtin_amdgcn_readfirstlane((int)pairs[w]);
+        v4i A[4];
+#pragma unroll
+        for (u32 f = 0; f < 4u; ++f) A[f] = bits16_to_bytes(a[f]);
+#pragma unroll
+        for (u32 f = 0; f < 4u; ++f) acc[f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[f], b0, acc[f], 0, 0, 0);
+        if (np > 1u) {  // (a count of 2^14 or more in this word: planes 2 and 3)
+            const v4i b1 = frag[((size_t)words_cap + w) * 64u + lane];
+#pragma unroll
+            for (u32 f = 0; f < 4u; ++f) acc2[f] = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[f], b1, acc2[f], 0, 0, 0);
+        }
+    }
+    // planes together: columns 0 - 7 hold the even planes of batches 0 - 7, columns 8 - 15 (eight lanes on) the odd ones
+#pragma unroll
+    for (u32 f = 0; f < 4u; ++f)
+#pragma unroll
+        for (u32 r = 0; r < 4u; ++r) {
+            const u32 v = (u32)acc[f][r] + ((u32)acc2[f][r] << 14);
+            const u32 up = (u32)__shfl_down((int)v, 8, 16);
+            if (gi < 8u) red[wv][gi][16u * f + 4u * q + r] = v + 128u * up;
+        }
+    __syncthreads();
+    for (u32 i = threadIdx.x; i < kPassBatchesMax * 64u; i += 256u) {
+        const u32 b = i >> 6, g = i & 63u;
+        const u32 v = red[0][b][g] + red[1][b][g] + red[2][b][g] + red[3][b][g];
+        if (b < n_b && v) gain[(size_t)b * n_pad + g0 + g] += v;
+    }
+}
 // ... and the rows behind the dense ones (rare hashes): cnt[b][row] to every genome on the hash's list: one walk over the lists, one
 // atomic per posting and batch the row occurs in.  (Device-scope atomics are executed at the memory side, ~2.3 G/s scattered: 8.7 M
 // postings per C2 pass of the SNP workload = 3.7 ms, most of them the ~200 genomes of SOME lineage whose lineage-level hash a
@@ -4840,29 +4946,6 @@ __global__ __launch_bounds__(256) void gain_sparse_kernel(const u32* __restrict_
                 for (u32 b = 0; b < kPassBatchesMax; ++b)
                     if (cc[b]) atomicAdd(&gain[((size_t)b * n_pad + g) * kGainSparseStride], cc[b]);
             }
-        }
-    }
-}
-// tab[0] = the table the pass starts from, tab[b + 1] = tab[b] + gain[b]
-// the long-list rows of every batch, compacted: lrow[b][i] = {bit row, sparse row} for the rows that occur in batch b
-__global__ __launch_bounds__(256) void long_rows_kernel(const u32* __restrict__ sslot, const u32* __restrict__ n_d, const u32* __restrict__ cnt,
-                                                        u32 row_stride, u32 n_b, LongRows lr) {
-    __builtin_amdgcn_s_setprio(3);
-    const u32 nd64 = n_d[2], ns = n_d[1], lane = lane_id();
-    for (u32 sr0 = (blockIdx.x * 256u + threadIdx.x) & ~63u; sr0 < ns; sr0 += gridDim.x * 256u) {
-        const u32 sr = sr0 + lane;
-        uint2 e = make_uint2(0u, 0u);
-        if (sr < ns) e = reinterpret_cast<const uint2*>(sslot)[sr];
-        const bool lng = (e.y & kLongFlag) != 0u;
-        if (!__ballot(lng)) continue;
-        for (u32 b = 0; b < n_b; ++b) {
-            const bool in = lng && cnt[(size_t)b * row_stride + nd64 + sr] != 0u;
-            const u64 bal = __ballot(in);
-            if (!bal) continue;
-            u32 base = 0;
-            if (lane == 0u) base = atomicAdd(&lr.nlrow[b * kCtrStride], (u32)__popcll(bal));
-            base = (u32)__shfl((int)base, 0);
-            if (in) lr.lrow[(size_t)b * lr.lrow_stride + base + (u32)__popcll(bal & lanemask_lt())] = make_uint2(e.x, sr);
         }
     }
 }
@@ -5969,8 +6052,39 @@ void launch_pass_hist(hipStream_t st, const u32* pair_q, const PassBatches& pb, 
     if (n == 0) return;
     hipLaunchKernelGGL(pass_hist_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, pair_q, pb, cnt, row_stride);
 }
+#ifdef SKX_EXPERIMENTS
+static std::atomic<unsigned long long> g_gain_launches[2];  // [0] as the int8 product, [1] bit by bit (skx_debug_gain_launches)
+void gain_dense_launches(unsigned long long* out, bool reset) {
+    for (int i = 0; i < 2; ++i) { out[i] = g_gain_launches[i].load(); if (reset) g_gain_launches[i] = 0; }
+}
+#endif
+bool gain_dense_by_bits() {
+#ifdef SKX_EXPERIMENTS
+    static const int mfma = env_int("SKX_GAIN_MFMA", 1);  // experiment knob: 0 = gain_dense_kernel<NB> for every call (A/B baseline)
+    return mfma == 0;
+#else
+    return false;
+#endif
+}
+size_t gain_operand_bytes(u32 words_cap) { return (size_t)2 * words_cap * kGopWordBytes; }
 void launch_gain_dense(hipStream_t st, const u64* m_bits, const u64* m_int, u32 n_pad, const u32* n_d, u32 rows_bound, const u32* cnt, u32 row_stride,
-                       u32 n_b, u32* gain, const u32* segw, const u32* grp_sp) {
+                       u32 n_b, u32* gain, const u32* segw, const u32* grp_sp, const GainOperand* op) {
+    // The int8 product takes every call it is given operand scratch for, except: the split scan's second array (m_int), more words than
+    // the scratch holds, more than kPassBatchesMax batches.  (int32 per plane: rows x 127 < 2^31 -- 2^22 rows at most, skx_capi.hip.)
+    if (op && op->frag && !m_int && !gain_dense_by_bits() && n_b <= kPassBatchesMax && cdiv(rows_bound, 64) <= op->words_cap && rows_bound <= (1u << 22)) {
+        const u32 words = std::max(1u, cdiv(rows_bound, 64));
+#ifdef SKX_EXPERIMENTS
+        g_gain_launches[0] += 1;
+#endif
+        hipLaunchKernelGGL(gain_operand_kernel, dim3(cdiv(words, 4)), dim3(256), 0, st, n_d, cnt, row_stride, n_b, reinterpret_cast<v4i*>(op->frag), op->pairs,
+                           op->words_cap);
+        hipLaunchKernelGGL(gain_dense_mfma_kernel, dim3(n_pad / 64), dim3(256), 0, st, m_bits, n_pad, n_d, reinterpret_cast<const v4i*>(op->frag), op->pairs,
+                           op->words_cap, words, n_b, gain, segw, grp_sp);
+        return;
+    }
+#ifdef SKX_EXPERIMENTS
+    g_gain_launches[1] += 1;
+#endif
     const dim3 grid(n_pad / 256, std::max(1u, cdiv(cdiv(rows_bound, 64), kGainWords)));
 #define SKX_GAIN(NB) hipLaunchKernelGGL(gain_dense_kernel<NB>, grid, dim3(256), 0, st, m_bits, m_int, n_pad, n_d, cnt, row_stride, gain, segw, grp_sp)
     switch (n_b) {
@@ -6028,9 +6142,6 @@ u32 pass_counter_bytes() { return kPassBatchesMax * kCtrStride * 4u; }
 void launch_mlong_build(hipStream_t st, const u32* lslot, u32 n_long, const u32* off, const u32* cnt, const u32* post, u64* mlong, u32 n_gw) {
     if (n_long == 0) return;
     hipLaunchKernelGGL(mlong_build_kernel, dim3(cdiv(n_long, 4)), dim3(256), 0, st, lslot, n_long, off, cnt, post, mlong, n_gw);
-}
-void launch_long_rows(hipStream_t st, const u32* sslot, const u32* n_d, u32 rows_bound, const u32* cnt, u32 row_stride, u32 n_b, const LongRows& lr) {
-    hipLaunchKernelGGL(long_rows_kernel, dim3(std::max(1u, std::min(cdiv(rows_bound, 256), (u32)env_int("SKX_G_LONGROWS", 1024)))), dim3(256), 0, st, sslot, n_d, cnt, row_stride, n_b, lr);
 }
 void launch_gain_long(hipStream_t st, const LongRows& lr, const RareIndex& ri, const u32* n_d, const u32* cnt, u32 row_stride, u32 n_b, u32 n_pad,
                       u32* gain_l, u32 walk_scale) {

@@ -124,7 +124,6 @@ u32 pat_words_max();  // genome words of a compact problem the pattern path hand
 struct LongRows { uint2* lrow; u32* nlrow; u32 lrow_stride; u64* inb = nullptr; u32 n_lw = 0; };  // inb[b][n_lw] (or NULL; zero on entry): bit r = bit row r is on batch b's list  // (nlrow: one counter per batch, pass_counter_bytes() in all)
 u32 pass_counter_bytes();  // size of the per-batch counter arrays of a pass (nlrow, nqc: one cache line per batch)
 void launch_mlong_build(hipStream_t st, const u32* lslot, u32 n_long, const u32* off, const u32* cnt, const u32* post, u64* mlong, u32 n_gw);
-void launch_long_rows(hipStream_t st, const u32* sslot, const u32* n_d, u32 rows_bound, const u32* cnt, u32 row_stride, u32 n_b, const LongRows& lr);
 // gain_l[b][g] (zero on entry) += sum over batch b's long-list rows of cnt x bit: bit-sliced counters over the rows' 64-bit words
 void launch_gain_long(hipStream_t st, const LongRows& lr, const RareIndex& ri, const u32* n_d, const u32* cnt, u32 row_stride, u32 n_b, u32 n_pad,
                       u32* gain_l, u32 walk_scale = 1);
@@ -177,9 +176,15 @@ void launch_pass_hist(hipStream_t st, const u32* pair_q, const PassBatches& pb, 
 // gain[b][g] (zero on entry) += sum over rows of cnt[b][row] * (row's bit for g): dense rows from m_bits (BEFORE the transpose
 // re-zeroes it), the others from the genome lists (ri / sslot, or NULL)
 // gain_s (zero on entry, [n_b][n_pad] entries gain_sparse_stride() words apart): the rare rows' part
+// op (or NULL): scratch for the counts as the int8 operand of the matrix product (gain_operand_kernel writes it, gain_dense_mfma_kernel
+// reads it, both inside this call) -- frag: gain_operand_bytes(words_cap) bytes, 16-byte aligned; pairs: [words_cap].  Nothing of it
+// is cleared or kept between calls.  Without it, with m_int, or with more than words_cap words of rows: the bit-by-bit kernel.
+struct GainOperand { void* frag; u32* pairs; u32 words_cap; };
+size_t gain_operand_bytes(u32 words_cap);
+bool gain_dense_by_bits();  // experiments build, SKX_GAIN_MFMA=0: the bit-by-bit kernel for every call (A/B baseline)
 void launch_gain_dense(hipStream_t st, const u64* m_bits, const u64* m_int /* or NULL */, u32 n_pad, const u32* n_d, u32 rows_bound, const u32* cnt,
                        u32 row_stride, u32 n_b, u32* gain, const u32* segw = nullptr /* [2 n_sp] word range of every species' rows (static dictionary) */,
-                       const u32* grp_sp = nullptr);
+                       const u32* grp_sp = nullptr, const GainOperand* op = nullptr);
 // (lr: also lists the rows with a bit row per batch, nlrow zero on entry; walk_scale: multiplies the workgroups of the list walk --
 // a pass with nothing beside it may fill the chip)
 // (pr: the rows whose list is pattern + exceptions add to hist / gain_x and are listed for launch_cand_pat_map; hist, gain_x, nprow zero on entry)

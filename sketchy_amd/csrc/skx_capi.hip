@@ -28,10 +28,13 @@
 #include <vector>
 
 #include "sketchy_hip.h"
+#include "skx_batch_out.hpp"
 #include "skx_common.hpp"
 #include "skx_genome_groups.hpp"
 #include "skx_kernels.hpp"
 
+using skx::BatchOut;
+using skx::EventList;
 using skx::u32;
 using skx::u64;
 
@@ -920,32 +923,6 @@ struct TimedSpan { int stage; hipEvent_t a, b; };
 // passes.  skx_stream_push* run both halves in one call; skx_stream_enqueue_device runs the front half of batch i + 1
 // BEFORE the back half of batch i, so the sketch stream never waits for the host between two batches.
 static const int kGroupMax = skx::kPairBaseMax + 1;  // batches that may share one pass (option stream_coalesce)
-// Event list of a batch (skx_stream_bind_changes): where its change points go.  In skx_stream::bound_chg the caller's arrays (whatever
-// memory the entry point takes); in a PendingBatch / SubPass DEVICE arrays, filled behind the batch's last pass.  cap == 0: none.
-struct ChangeOut {
-    u32 cap = 0;
-    u32 n_batch = 0;  // reads of the batch: the sub-pass that ends there queues the scan and the gather
-    u32 *n_events = nullptr, *ev_read = nullptr, *ev_idx = nullptr;
-    u64* ev_sum = nullptr;
-    u32* ev_codes = nullptr;
-    bool codes = false;  // the call of a read is its consensus codes, not its index row
-};
-// Species call of a batch (skx_stream_bind_call: on; skx_stream_bind_call_changes: cap != 0), travelling like ChangeOut: the caller's
-// arrays in skx_stream::bound_call, DEVICE arrays in a PendingBatch / SubPass.  Compact rows nobody asked for but the event list
-// needs go to the ranking lane's scratch.
-struct CallOut {
-    bool on = false;
-    u32 *sp = nullptr, *idx = nullptr;
-    u64* sum = nullptr;
-    u32* codes = nullptr;
-    u32 cap = 0;
-    u32 n_batch = 0;
-    u32 *n_events = nullptr, *ev_read = nullptr, *ev_sp = nullptr, *ev_idx = nullptr;
-    u64* ev_sum = nullptr;
-    u32* ev_codes = nullptr;  // non-NULL: the compared part of the call is its codes
-    bool any() const { return on || cap != 0; }
-    bool wants_codes() const { return codes != nullptr || ev_codes != nullptr; }
-};
 struct PendingBatch {
     bool valid = false;
     int side = 0;  // which copy of the sketch buffers holds it
@@ -971,9 +948,7 @@ struct PendingBatch {
     u64* h_sketches = nullptr;
     u32* h_sketch_len = nullptr;
     void* slot = nullptr;      // skx_stream::Staged of a host-fed batch: its rows travel to the host behind the ranking
-    u32* d_cons = nullptr;     // [n_reads][n_species][n_features] consensus codes of its rows (skx_stream_bind_consensus) or NULL
-    ChangeOut chg;             // its event list (skx_stream_bind_changes)
-    CallOut call;              // its species call (skx_stream_bind_call, skx_stream_bind_call_changes)
+    BatchOut out;              // its bound outputs (skx_batch_out.hpp): DEVICE arrays, filled behind the ranking of its passes
 };
 
 // The HIP streams of the pipeline, ONE set per device shared by every skx_stream on it.  Measured (tools/diag_second_stream.py,
@@ -1010,10 +985,18 @@ struct SubPass {
     u32* d_counts = nullptr;      // [rb-ra][n_pad] or NULL: the same counts in padded genome order, from the bit-sliced counter (skx_rank_sketches)
     int side = 0;
     void* slot = nullptr;         // host-fed batches: the staging slot whose rows go back to the host behind the ranking
-    u32* d_cons = nullptr;        // consensus codes of the BATCH's rows (row 0 = the batch's first read) or NULL
-    ChangeOut chg;                // the BATCH's event list: flags for [ra, rb) here, scan + gather when rb ends the batch
-    CallOut call;                 // the BATCH's species call: selection and flags for [ra, rb) here, scan + gather when rb ends the batch
+    BatchOut out;                 // the BATCH's bound outputs (row 0 = the batch's first read): votes, selection and flags for [ra, rb)
+                                  // here, the scans and the gathers when rb ends the batch
 };
+// Device copies of the bound outputs of HOST-fed batches (skx_stream_push: the stream's, skx_stream_submit: one per staging slot) and the
+// page-locked words their two n_events travel back in.  Everything is allocated by the first batch that needs it (ensure_out); the
+// event arrays grow with the caps asked for.
+struct HostFedOut {
+    BatchOut d;
+    u32* h_n[2] = {nullptr, nullptr};  // [0] the change list's n_events, [1] the call's
+};
+// What a ranking lane needs to compact one event list: a flag and a position per read of a batch, the scan's block totals
+struct EventScratch { u32 *flag = nullptr, *pos = nullptr, *bsum = nullptr; };
 static const int kSides = kGroupMax + 1;  // copies of the per-batch sketch outputs: the enqueued batches waiting for their shared pass + the one being sketched
                                           // (a stream uses stream_coalesce + 1 of them, allocated at first use)
 static const u32 kStagedGroupMax = 4;
@@ -1268,13 +1251,12 @@ struct skx_stream {
         u64 *d_cand_sum = nullptr;
         u32 *d_cand_idx = nullptr;
         u64 *d_cum_sink = nullptr;  // [n_pad] the table the chain's prefix kernels write (round 5: the real one comes from the pass's gains)
-        // change points (skx_stream_bind_changes; allocated by the first bound batch the lane ranks): one flag and one position per read
-        // of a batch, the scan's block totals, and -- codes mode of a _device entry point without a consensus output -- the codes voted on
-        u32 *d_chg_flag = nullptr, *d_chg_pos = nullptr, *d_chg_bsum = nullptr, *d_chg_codes = nullptr;
-        // species call (skx_stream_bind_call, skx_stream_bind_call_changes; each allocated by the first bound batch that needs it): flag,
-        // position and key {species, index row | codes} per read for the event list, and the compact rows an event list gathers from
-        // when the batch's call itself was not bound or leaves them out
-        u32 *d_call_flag = nullptr, *d_call_pos = nullptr, *d_call_bsum = nullptr, *d_call_key = nullptr;
+        // bound outputs (queue_bound_outputs; each allocated by the first bound batch of the lane that needs it): the scratch of the change
+        // list and of the call's list; the codes voted on when a _device entry point needs them without a consensus output; the call's
+        // key {species, index row | codes} per read, and the compact rows its event list gathers from when the batch's call itself was
+        // not bound or leaves them out
+        EventScratch chg_scr, call_scr;
+        u32 *d_vote = nullptr, *d_call_key = nullptr;
         u32 *d_call_sp = nullptr, *d_call_idx = nullptr, *d_call_codes = nullptr;
         u64* d_call_sum = nullptr;
         u32 call_key_w = 0;  // words per read d_call_key has room for: it grows when a wider key arrives (a genotype table set after the first rows-mode list)
@@ -1294,19 +1276,10 @@ struct skx_stream {
     u64* d_cum = nullptr;        // running table (current)
     u32* d_topk_idx = nullptr;
     u64* d_topk_sum = nullptr;
-    // consensus codes (skx_stream_bind_consensus): the output bound for the next batch call, and the device buffer a bound
-    // skx_stream_push writes them to ([max_reads][n_species][n_features], allocated by the first such push)
-    u32* bound_cons = nullptr;
-    u32* d_cons = nullptr;
-    // event list (skx_stream_bind_changes): the arrays bound for the next batch call, and the device copy a bound skx_stream_push
-    // gathers into (d_ev: {n_events, ev_read, ev_idx, ev_sum, ev_codes} for d_ev.cap entries; grows with the caps asked for)
-    ChangeOut bound_chg;
-    ChangeOut d_ev;
-    // species call (skx_stream_bind_call, skx_stream_bind_call_changes): the arrays bound for the next batch call, and the device copy a
-    // bound skx_stream_push selects and gathers into (rows for max_reads reads, events for d_call.cap entries; each array allocated
-    // by the first push that asks for it)
-    CallOut bound_call;
-    CallOut d_call;
+    // bound outputs (skx_stream_bind_consensus, _changes, _call, _call_changes): the caller's arrays bound for the next batch call, and
+    // the device copies a bound skx_stream_push writes (codes and compact rows for max_reads reads, events for the caps asked for)
+    BatchOut bound;
+    HostFedOut push_out;
     u64* d_tab_tmp = nullptr;   // [n_genomes] staging of skx_stream_table / skx_stream_table_add
     u32* d_rank_idx = nullptr;  // [n_species][top] outputs of skx_stream_rank
     u64* d_rank_sum = nullptr;
@@ -1352,14 +1325,9 @@ struct skx_stream {
         u64 n_bases = 0, ticket = 0;
         u32* out_idx = nullptr;
         u64* out_sum = nullptr;
-        u32* out_cons = nullptr;    // consensus codes of the batch (page-locked host) or NULL; d_cons: the slot's device copy, allocated
-        u32* d_cons = nullptr;      // for every slot by the first bound submit
-        ChangeOut out_chg;          // event list of the batch (the caller's page-locked arrays) or cap == 0; d_ev: the slot's device copy
-        ChangeOut d_ev;             // (allocated by the slot's first bound submit, grows with the caps asked for); h_ev_n: page-locked, the
-        u32* h_ev_n = nullptr;      // batch's n_events on its way back -- the host copies min(n_events, cap) entries once it is there
-        CallOut out_call;           // species call of the batch (the caller's page-locked arrays), d_call: the slot's device copy,
-        CallOut d_call;             // h_cev_n: its n_events on the way back -- as out_chg, d_ev and h_ev_n
-        u32* h_cev_n = nullptr;
+        BatchOut out;               // bound outputs of the batch (the caller's page-locked arrays); dev: the slot's device copies (the codes
+        HostFedOut dev;             // for every slot by the first submit with a consensus output, the rest by the slot's first bound submit
+                                    // that needs it) -- the host copies min(n_events, cap) entries of a list once its n_events is there
         u32* d_rows_idx = nullptr;  // the slot's own device rows (batches may share a pass: each needs its rows until they are copied out)
         u64* d_rows_sum = nullptr;
         uint8_t* d_bases = nullptr;
@@ -1384,10 +1352,21 @@ struct skx_stream {
 
 static void free_side(skx_stream* st, int i);
 static void free_lane(skx_stream* st, int i);
-static void free_call(CallOut& d) {
-    void* ptrs[] = {d.sp, d.idx, d.sum, d.codes, d.n_events, d.ev_read, d.ev_sp, d.ev_idx, d.ev_sum, d.ev_codes};
-    for (void* q : ptrs) (void)hipFree(q);
-    d = CallOut{};
+static void free_events(EventList& d) {
+    for (void* q : {(void*)d.n_events, (void*)d.ev_read, (void*)d.ev_sp, (void*)d.ev_idx, (void*)d.ev_sum, (void*)d.ev_codes}) (void)hipFree(q);
+    d = EventList{};
+}
+static void free_out(HostFedOut& o) {
+    for (void* q : {(void*)o.d.cons, (void*)o.d.call.sp, (void*)o.d.call.idx, (void*)o.d.call.sum, (void*)o.d.call.codes}) (void)hipFree(q);
+    free_events(o.d.chg);
+    free_events(o.d.call_ev);
+    for (u32* h : o.h_n)
+        if (h) (void)hipHostFree(h);
+    o = HostFedOut{};
+}
+static void free_scratch(EventScratch& s) {
+    (void)hipFree(s.flag); (void)hipFree(s.pos); (void)hipFree(s.bsum);
+    s = EventScratch{};
 }
 static void stream_free(skx_stream* st) {
     if (!st) return;
@@ -1402,7 +1381,7 @@ static void stream_free(skx_stream* st) {
     void* ptrs[] = {st->d_bases, st->d_offsets, st->d_pair_h[0], st->d_pair_h[1],
                     st->d_q[0], st->d_q[1], st->d_pair_r[0], st->d_pair_r[1], st->d_pair_q[0], st->d_pair_q[1],
                     st->d_poff_pass[0], st->d_poff_pass[1], st->d_poff_pass[2], st->d_pair_r[2], st->d_nq[0], st->d_nq[1], st->d_win[0], st->d_win[1], st->d_m, st->d_mint, st->d_mq[0], st->d_mq[1],
-                    st->d_topk_idx, st->d_topk_sum, st->d_cons, st->d_ev.n_events, st->d_ev.ev_read, st->d_ev.ev_idx, st->d_ev.ev_sum, st->d_ev.ev_codes, st->d_tab_tmp, st->d_rank_idx, st->d_rank_sum, st->d_bsum, st->d_grp_any[0],
+                    st->d_topk_idx, st->d_topk_sum, st->d_tab_tmp, st->d_rank_idx, st->d_rank_sum, st->d_bsum, st->d_grp_any[0],
                     st->d_grp_any[1], st->d_hbuf, st->d_wb[0], st->d_wb[1], st->d_rowany[0], st->d_rowany[1], st->d_mqext,
                     st->d_qd, st->d_qrow, st->d_sslot, st->d_qinfo, st->d_qloc, st->d_cls_bsum, st->d_nd_hs,
                     st->d_rowcnt, st->d_gain, st->d_gain_s, st->d_candslot, st->d_candmask, st->d_lrow, st->d_gop, st->d_gop_pairs, st->d_nlrow, st->d_gain_l, st->d_cbase, st->d_cwl, st->d_ncwl, st->d_cw, st->d_cbad, st->d_nqc, st->d_spc_g0, st->d_spc_grp, st->d_inb, st->d_hit, st->d_hist, st->d_nprow, st->d_pcw, st->d_ms[0], st->d_ms[1], st->d_mdirty_s};
@@ -1432,13 +1411,10 @@ static void stream_free(skx_stream* st) {
     (void)hipFree(st->d_ht[0]); (void)hipFree(st->d_ht[1]); (void)hipFree(st->d_dict_ctr[0]); (void)hipFree(st->d_dict_ctr[1]);
     (void)hipFree(st->d_slot_off); (void)hipFree(st->d_bcount); (void)hipFree(st->d_bbase);
     (void)hipFree(st->d_btot);
-    free_call(st->d_call);
+    free_out(st->push_out);
     for (auto& sl : st->slot) {
-        free_call(sl.d_call);
-        if (sl.h_cev_n) (void)hipHostFree(sl.h_cev_n);
-        (void)hipFree(sl.d_bases); (void)hipFree(sl.d_offsets); (void)hipFree(sl.d_rows_idx); (void)hipFree(sl.d_rows_sum); (void)hipFree(sl.d_cons);
-        (void)hipFree(sl.d_ev.n_events); (void)hipFree(sl.d_ev.ev_read); (void)hipFree(sl.d_ev.ev_idx); (void)hipFree(sl.d_ev.ev_sum); (void)hipFree(sl.d_ev.ev_codes);
-        if (sl.h_ev_n) (void)hipHostFree(sl.h_ev_n);
+        free_out(sl.dev);
+        (void)hipFree(sl.d_bases); (void)hipFree(sl.d_offsets); (void)hipFree(sl.d_rows_idx); (void)hipFree(sl.d_rows_sum);
         if (sl.h_offsets) (void)hipHostFree(sl.h_offsets);
         if (sl.ev_copy) (void)hipEventDestroy(sl.ev_copy);
         if (sl.ev_done) (void)hipEventDestroy(sl.ev_done);
@@ -1587,9 +1563,10 @@ static void free_lane(skx_stream* st, int i) {
     skx_stream::RankLane& L = st->lane[i];
     void* ptrs[] = {L.d_inc, L.d_rel, L.d_live, L.d_has, L.d_lead_seg, L.d_live_ctr, L.d_csum, L.d_csum_raw, L.d_leader, L.d_lead_val,
                     L.d_lpart_sum, L.d_lpart_idx, L.d_gmax, L.d_cand_sum, L.d_cand_idx, L.d_cum_sink,
-                    L.d_chg_flag, L.d_chg_pos, L.d_chg_bsum, L.d_chg_codes,
-                    L.d_call_flag, L.d_call_pos, L.d_call_bsum, L.d_call_key, L.d_call_sp, L.d_call_idx, L.d_call_codes, L.d_call_sum};
+                    L.d_vote, L.d_call_key, L.d_call_sp, L.d_call_idx, L.d_call_codes, L.d_call_sum};
     for (void* q : ptrs) (void)hipFree(q);
+    free_scratch(L.chg_scr);
+    free_scratch(L.call_scr);
     if (L.ev_cum) (void)hipEventDestroy(L.ev_cum);
     if (L.ev_done) (void)hipEventDestroy(L.ev_done);
     const hipStream_t keep = L.s;  // (streams are created and destroyed with the skx_stream, not with the scratch)
@@ -2641,6 +2618,94 @@ static int queue_chains(skx_stream* st, bool block) {
     }
     return SKX_OK;
 }
+// ---- the bound outputs of a batch (skx_batch_out.hpp) behind the ranking of one of its sub-passes
+template <class T>
+static int lazy_alloc(T*& p, size_t bytes) {
+    if (!p) HIPCHK(hipMalloc(&p, bytes));
+    return SKX_OK;
+}
+static int need_scratch(EventScratch& s, size_t max_reads) {
+    if (s.flag) return SKX_OK;
+    HIPCHK(hipMalloc(&s.flag, max_reads * 4));
+    HIPCHK(hipMalloc(&s.pos, max_reads * 4));
+    HIPCHK(hipMalloc(&s.bsum, (max_reads / 1024 + 1) * 4));
+    return SKX_OK;
+}
+// One event list: the flags of the reads [ra, rb) the sub-pass has just finished (rows [.][width]: what two reads are compared by); behind
+// the batch's last sub-pass the scan, and the gather of the columns asked for out of src_*
+static void queue_events(hipStream_t ls, const EventScratch& s, const EventList& ev, const SubPass& sb, const u32* rows, u32 width,
+                         const u32* src_idx, const u64* src_sum, u32 w_idx, const u32* src_codes, u32 w_codes) {
+    skx::launch_change_flags(ls, rows, width, sb.ra, sb.rb, s.flag);
+    if (sb.rb == ev.n_batch)
+        skx::launch_change_events(ls, s.flag, s.pos, s.bsum, ev.n_batch, ev.cap, ev.n_events, ev.ev_read, ev.ev_idx ? src_idx : nullptr,
+                                  ev.ev_sum ? src_sum : nullptr, w_idx, ev.ev_idx, ev.ev_sum, ev.ev_codes ? src_codes : nullptr, w_codes, ev.ev_codes);
+}
+// Everything the batch's record asks for over the rows [ra, rb) this sub-pass has just finished, on the lane's stream behind the last
+// kernel that writes them: the vote, the change list, the species call and its list.  Flags go with every sub-pass, the scans and the
+// gathers behind the batch's last one.  Row ra - 1 of a batch cut into passes was written by the pass before: passes of one batch are
+// passes of their own (n_sub == 1) and run on lane 0 one behind the other, and the batches of a shared pass begin at read 0, which
+// compares with nothing.
+static int queue_bound_outputs(skx_stream* st, skx_stream::RankLane& L, hipStream_t ls, const SubPass& sb, u32* d_topk_idx, u64* d_topk_sum) {
+    const BatchOut& o = sb.out;
+    if (!o.any()) return SKX_OK;
+    if ((o.chg.cap || o.call_ev.cap) && sb.ra != 0 && &L != &st->lane[0]) return fail(SKX_ERR_HIP, "internal: a later pass of a batch left lane 0");
+    const skx_ref* ref = st->ref;
+    const u32 n_sp = ref->n_species, nf = ref->n_features, top = st->top_k;
+    const size_t mr = st->max_reads;
+    u32* d_vote = nullptr;  // where the codes of this sub-pass's rows are, once somebody has voted
+    auto voted = [&]() -> int {
+        if (d_vote) return SKX_OK;
+        d_vote = o.cons;
+        if (!d_vote) {  // (no consensus output travels with the batch: the vote goes to the lane's own scratch)
+            SKXCHK(lazy_alloc(L.d_vote, mr * n_sp * nf * 4));
+            d_vote = L.d_vote;
+        }
+        skx::launch_consensus_rows(ls, d_topk_idx, sb.ra, sb.rb - sb.ra, n_sp, top, ref->d_sp_g0, ref->d_codes, nf, d_vote, ref->n_pad);
+        return SKX_OK;
+    };
+    if (o.cons) SKXCHK(voted());
+    if (o.chg.cap) {
+        SKXCHK(need_scratch(L.chg_scr, mr));
+        const skx::RowWidths w = skx::change_widths(n_sp, top, nf);
+        if (o.chg.codes()) SKXCHK(voted());
+        const u32* d_codes = o.chg.codes() ? d_vote : nullptr;
+        queue_events(ls, L.chg_scr, o.chg, sb, d_codes ? d_codes : d_topk_idx, (u32)(d_codes ? w.codes : w.idx), d_topk_idx, d_topk_sum, (u32)w.idx,
+                     d_codes, (u32)w.codes);
+    }
+    if (o.wants_call()) {
+        const EventList& ev = o.call_ev;
+        const bool with_codes = o.call.codes || ev.codes();
+        if (with_codes) SKXCHK(voted());
+        // where the compact rows go: the bound arrays, or -- an event list needs rows the call leaves out -- the lane's scratch
+        u32 *c_sp = o.call.sp, *c_idx = o.call.idx, *c_codes = o.call.codes, *c_key = nullptr;
+        u64* c_sum = o.call.sum;
+        if (!c_sp) { SKXCHK(lazy_alloc(L.d_call_sp, mr * 4)); c_sp = L.d_call_sp; }
+        if (ev.cap) {
+            SKXCHK(need_scratch(L.call_scr, mr));
+            // (the reference may get its genotype table after this lane's first event list: the key of a codes-mode list is then wider
+            // than the room sized before.  A batch's passes all have one width, so the key never grows inside a batch; hipFree waits
+            // for whatever the lane still has queued)
+            const u32 key_w = 1u + std::max(top, nf);
+            if (L.call_key_w < key_w) {
+                (void)hipFree(L.d_call_key);
+                L.d_call_key = nullptr; L.call_key_w = 0;
+                HIPCHK(hipMalloc(&L.d_call_key, mr * key_w * 4));
+                L.call_key_w = key_w;
+            }
+            c_key = L.d_call_key;
+            if (ev.ev_idx && !c_idx) { SKXCHK(lazy_alloc(L.d_call_idx, mr * top * 4)); c_idx = L.d_call_idx; }
+            if (ev.ev_sum && !c_sum) { SKXCHK(lazy_alloc(L.d_call_sum, mr * top * 8)); c_sum = L.d_call_sum; }
+            if (ev.ev_codes && !c_codes) { SKXCHK(lazy_alloc(L.d_call_codes, mr * nf * 4)); c_codes = L.d_call_codes; }
+        }
+        skx::launch_species_call(ls, d_topk_idx, d_topk_sum, with_codes ? d_vote : nullptr, sb.ra, sb.rb, n_sp, top, nf, c_sp, c_idx, c_sum, c_codes,
+                                 c_key, ev.codes());
+        if (ev.cap) {
+            queue_events(ls, L.call_scr, ev, sb, c_key, 1u + (ev.codes() ? nf : top), c_idx, c_sum, top, c_codes, nf);
+            if (sb.rb == ev.n_batch && ev.ev_sp) skx::launch_call_species_gather(ls, L.call_scr.flag, L.call_scr.pos, ev.n_batch, ev.cap, c_sp, ev.ev_sp);
+        }
+    }
+    return SKX_OK;
+}
 static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, bool* done) {
     *done = false;
     if (!pc.pending) { *done = true; return SKX_OK; }
@@ -2817,104 +2882,7 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
         if (compact)  // candidate slots -> genome indices (local to the species)
             skx::launch_cand_rows_back(ls, d_topk_idx + (size_t)out_r0 * n_sp * st->top_k, n_reads, n_sp, st->top_k,
                                        ps.cand + (size_t)si * st->n_pad_c, skx::kCandCap, ref->d_sp_g0);
-        if (sb.d_cons)  // the vote over the rows this sub-pass has just finished, behind the last kernel that writes them
-            skx::launch_consensus_rows(ls, d_topk_idx, out_r0, n_reads, n_sp, st->top_k, ref->d_sp_g0, ref->d_codes, ref->n_features,
-                                       sb.d_cons, n_pad);
-        u32* d_vote = sb.d_cons;  // where the codes of this sub-pass's rows are, once somebody has voted
-        if (sb.chg.cap) {
-            // change points of the batch: flags for the reads this sub-pass has just finished, behind the last kernel that writes their
-            // rows (or codes); the scan and the gather behind the batch's last sub-pass.  Row ra - 1 of a batch cut into passes was
-            // written by the pass before: passes of one batch are passes of their own (n_sub == 1) and run on lane 0 one behind the
-            // other, and the batches of a shared pass begin at read 0, which compares with nothing.
-            if (sb.ra != 0 && li != 0) return fail(SKX_ERR_HIP, "internal: a later pass of a batch left lane 0");
-            if (!L.d_chg_flag) {
-                HIPCHK(hipMalloc(&L.d_chg_flag, (size_t)st->max_reads * 4));
-                HIPCHK(hipMalloc(&L.d_chg_pos, (size_t)st->max_reads * 4));
-                HIPCHK(hipMalloc(&L.d_chg_bsum, ((size_t)st->max_reads / 1024 + 1) * 4));
-            }
-            const u32 w_idx = n_sp * st->top_k, w_codes = n_sp * ref->n_features;
-            u32* d_codes = nullptr;
-            if (sb.chg.codes) {
-                d_codes = sb.d_cons;
-                if (!d_codes) {  // (no consensus output travels with the batch: the vote goes to the lane's own scratch)
-                    if (!L.d_chg_codes) HIPCHK(hipMalloc(&L.d_chg_codes, (size_t)st->max_reads * w_codes * 4));
-                    d_codes = L.d_chg_codes;
-                    skx::launch_consensus_rows(ls, d_topk_idx, out_r0, n_reads, n_sp, st->top_k, ref->d_sp_g0, ref->d_codes, ref->n_features,
-                                               d_codes, n_pad);
-                }
-            }
-            skx::launch_change_flags(ls, d_codes ? d_codes : d_topk_idx, d_codes ? w_codes : w_idx, sb.ra, sb.rb, L.d_chg_flag);
-            if (sb.rb == sb.chg.n_batch)
-                skx::launch_change_events(ls, L.d_chg_flag, L.d_chg_pos, L.d_chg_bsum, sb.chg.n_batch, sb.chg.cap, sb.chg.n_events,
-                                          sb.chg.ev_read, sb.chg.ev_idx ? d_topk_idx : nullptr, sb.chg.ev_sum ? d_topk_sum : nullptr, w_idx,
-                                          sb.chg.ev_idx, sb.chg.ev_sum, sb.chg.ev_codes ? d_codes : nullptr, w_codes, sb.chg.ev_codes);
-            if (d_codes) d_vote = d_codes;
-        }
-        if (sb.call.any()) {
-            // species call of the batch: the selection over the reads this sub-pass has just finished, behind the last kernel that writes
-            // their rows (or codes), with its flags; the scan and the gathers behind the batch's last sub-pass -- as the change points above
-            const CallOut& co = sb.call;
-            if (co.cap && sb.ra != 0 && li != 0) return fail(SKX_ERR_HIP, "internal: a later pass of a batch left lane 0");
-            const u32 nf = ref->n_features, key_w = 1u + std::max(st->top_k, nf);
-            const size_t mr = st->max_reads;
-            u32* d_codes = nullptr;
-            if (co.wants_codes()) {
-                d_codes = d_vote;
-                if (!d_codes) {  // (no consensus output travels with the batch: the vote goes to the lane's own scratch)
-                    if (!L.d_chg_codes) HIPCHK(hipMalloc(&L.d_chg_codes, mr * n_sp * nf * 4));
-                    d_codes = L.d_chg_codes;
-                    skx::launch_consensus_rows(ls, d_topk_idx, out_r0, n_reads, n_sp, st->top_k, ref->d_sp_g0, ref->d_codes, nf, d_codes, n_pad);
-                }
-            }
-            // where the compact rows go: the bound arrays, or -- an event list needs rows the call leaves out -- the lane's scratch
-            u32 *c_sp = co.sp, *c_idx = co.idx, *c_codes = co.codes, *c_key = nullptr;
-            u64* c_sum = co.sum;
-            if (!c_sp) {
-                if (!L.d_call_sp) HIPCHK(hipMalloc(&L.d_call_sp, mr * 4));
-                c_sp = L.d_call_sp;
-            }
-            if (co.cap) {
-                if (!L.d_call_flag) {
-                    HIPCHK(hipMalloc(&L.d_call_flag, mr * 4));
-                    HIPCHK(hipMalloc(&L.d_call_pos, mr * 4));
-                    HIPCHK(hipMalloc(&L.d_call_bsum, (mr / 1024 + 1) * 4));
-                }
-                // (the reference may get its genotype table after this lane's first event list: the key of a codes-mode list is then wider
-                // than the room sized before.  A batch's passes all have one width, so the key never grows inside a batch; hipFree waits
-                // for whatever the lane still has queued)
-                if (L.call_key_w < key_w) {
-                    (void)hipFree(L.d_call_key);
-                    L.d_call_key = nullptr; L.call_key_w = 0;
-                    HIPCHK(hipMalloc(&L.d_call_key, mr * key_w * 4));
-                    L.call_key_w = key_w;
-                }
-                c_key = L.d_call_key;
-                if (co.ev_idx && !c_idx) {
-                    if (!L.d_call_idx) HIPCHK(hipMalloc(&L.d_call_idx, mr * st->top_k * 4));
-                    c_idx = L.d_call_idx;
-                }
-                if (co.ev_sum && !c_sum) {
-                    if (!L.d_call_sum) HIPCHK(hipMalloc(&L.d_call_sum, mr * st->top_k * 8));
-                    c_sum = L.d_call_sum;
-                }
-                if (co.ev_codes && !c_codes) {
-                    if (!L.d_call_codes) HIPCHK(hipMalloc(&L.d_call_codes, mr * nf * 4));
-                    c_codes = L.d_call_codes;
-                }
-            }
-            const bool key_codes = co.ev_codes != nullptr;
-            skx::launch_species_call(ls, d_topk_idx, d_topk_sum, d_codes, sb.ra, sb.rb, n_sp, st->top_k, nf, c_sp, c_idx, c_sum, c_codes, c_key,
-                                     key_codes);
-            if (co.cap) {
-                skx::launch_change_flags(ls, c_key, 1u + (key_codes ? nf : st->top_k), sb.ra, sb.rb, L.d_call_flag);
-                if (sb.rb == co.n_batch) {
-                    skx::launch_change_events(ls, L.d_call_flag, L.d_call_pos, L.d_call_bsum, co.n_batch, co.cap, co.n_events, co.ev_read,
-                                              co.ev_idx ? c_idx : nullptr, co.ev_sum ? c_sum : nullptr, st->top_k, co.ev_idx, co.ev_sum,
-                                              co.ev_codes ? c_codes : nullptr, nf, co.ev_codes);
-                    if (co.ev_sp) skx::launch_call_species_gather(ls, L.d_call_flag, L.d_call_pos, co.n_batch, co.cap, c_sp, co.ev_sp);
-                }
-            }
-        }
+        SKXCHK(queue_bound_outputs(st, L, ls, sb, d_topk_idx, d_topk_sum));
     }
     if (sb.d_shared)
         skx::launch_shared_debug(ls, d_pair_q + sb.p_off, sub_poff, sub_base, 0, n_reads, d_mq, nq_rows, ref->n_genomes, ref->d_real2pad, sb.d_shared, 0);
@@ -2952,12 +2920,10 @@ static int queue_one(skx_stream* st, skx_stream::PassChains& pc, bool block, boo
 
 static int run_pass(skx_stream* st, u32 ra, u32 rb, u32 p_base, u32 P, u32* d_topk_idx, u64* d_topk_sum,
                     u32* d_shared /* [rb-ra][n_genomes] or NULL */, bool update_table, bool inserted = false, u32 q_rows = 0xFFFFFFFFu,
-                    void* slot = nullptr, u32* d_counts = nullptr /* [rb-ra][n_pad] or NULL */, u32* d_cons = nullptr,
-                    const ChangeOut* chg = nullptr, const CallOut* call = nullptr) {
+                    void* slot = nullptr, u32* d_counts = nullptr /* [rb-ra][n_pad] or NULL */, const BatchOut* out = nullptr) {
     SubPass sb;
-    sb.slot = slot; sb.d_cons = d_cons;
-    if (chg) sb.chg = *chg;
-    if (call) sb.call = *call;
+    sb.slot = slot;
+    if (out) sb.out = *out;
     sb.ra = ra; sb.rb = rb; sb.p_off = 0; sb.P = P; sb.p_base = p_base; sb.d_topk_idx = d_topk_idx; sb.d_topk_sum = d_topk_sum;
     sb.d_shared = d_shared; sb.d_counts = d_counts; sb.side = st->side;
     sb.d_poff = st->d_poff_pass[st->pslot];  // (inserted passes: the front half's copy; else run_pass_multi fills the slot itself)
@@ -3354,7 +3320,7 @@ static int batch_back(skx_stream* st, PendingBatch& pb, PendingBatch* younger) {
             HIPCHK(hipMalloc(&d_shared, (size_t)(rb - ra) * ref->n_genomes * 4));
         }
         SKXCHK(run_pass(st, ra, rb, p_base, P, pb.d_topk_idx, pb.d_topk_sum, d_shared, true, inserted, inserted ? q_rows : 0xFFFFFFFFu,
-                        rb == n_reads ? pb.slot : nullptr, nullptr, pb.d_cons, &pb.chg, &pb.call));
+                        rb == n_reads ? pb.slot : nullptr, nullptr, &pb.out));
         inserted = false;
         st->last_passes += 1;
         if (pb.h_shared) {
@@ -3461,7 +3427,7 @@ static int batch_back_group(skx_stream* st, PendingBatch* g, int n, PendingBatch
         subs[i].d_topk_idx = g[i].d_topk_idx; subs[i].d_topk_sum = g[i].d_topk_sum;
         subs[i].p_off = p_off; subs[i].P = P[i];
         subs[i].d_poff = st->d_poff_pass[g[0].spec_slot] + (size_t)i * ((size_t)st->rpass + 2);
-        subs[i].slot = g[i].slot; subs[i].d_cons = g[i].d_cons; subs[i].chg = g[i].chg; subs[i].call = g[i].call;
+        subs[i].slot = g[i].slot; subs[i].out = g[i].out;
         p_off += P[i];
     }
     st->last_pairs = pairs; st->last_passes = 1; st->shared_passes += 1;
@@ -3503,19 +3469,22 @@ static int flush_pending(skx_stream* st) {
     if (rc != SKX_OK) { g_err = msg; return rc; }
     return rc2;
 }
+// a batch of n_reads reads with its bound outputs (DEVICE arrays, or NULL: none)
+static PendingBatch pending_batch(u32 n_reads, const BatchOut* out) {
+    PendingBatch pb;
+    if (out) { pb.out = *out; pb.out.set_batch(n_reads); }
+    return pb;
+}
 // sketch + score + rank a batch already resident on the device, both halves (synchronous entry points).
 // h_shared / h_sketches / h_sketch_len: optional HOST outputs (parity/debug).
 static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_offsets, u32 n_reads, u64 n_bases, u32* d_topk_idx,
-                         u64* d_topk_sum, u32* h_shared, u64* h_sketches, u32* h_sketch_len, u32* d_cons = nullptr,
-                         const ChangeOut* chg = nullptr, const CallOut* call = nullptr) {
+                         u64* d_topk_sum, u32* h_shared, u64* h_sketches, u32* h_sketch_len, const BatchOut* out = nullptr) {
     if (n_reads == 0) return SKX_OK;
     SKXCHK(flush_pending(st));
-    PendingBatch pb;
+    PendingBatch pb = pending_batch(n_reads, out);
     pb.d_bases = d_bases; pb.d_offsets = d_offsets; pb.n_reads = n_reads; pb.n_bases = n_bases;
     pb.d_topk_idx = d_topk_idx; pb.d_topk_sum = d_topk_sum;
-    pb.h_shared = h_shared; pb.h_sketches = h_sketches; pb.h_sketch_len = h_sketch_len; pb.d_cons = d_cons;
-    if (chg) { pb.chg = *chg; pb.chg.n_batch = n_reads; }
-    if (call) { pb.call = *call; pb.call.n_batch = n_reads; }
+    pb.h_shared = h_shared; pb.h_sketches = h_sketches; pb.h_sketch_len = h_sketch_len;
     SKXCHK(batch_front(st, pb));
     st->tail_pass = true;  // (a synchronous push: the batch's passes have the chip to themselves)
     const int rc = batch_back(st, pb, nullptr);
@@ -3527,11 +3496,8 @@ static int process_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_of
 // next group runs the shared back half of the one before it, behind its own front half.  Errors of a batch surface here up to
 // stream_coalesce calls late (or in the flush); the batches enqueued after it up to that call are dropped too.
 static int enqueue_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_offsets, u32 n_reads, u64 n_bases, u32* d_topk_idx,
-                         u64* d_topk_sum, void* slot, u32* d_cons, const ChangeOut* chg = nullptr, const CallOut* call = nullptr) {
-    PendingBatch nw;
-    nw.d_cons = d_cons;
-    if (chg) { nw.chg = *chg; nw.chg.n_batch = n_reads; }
-    if (call) { nw.call = *call; nw.call.n_batch = n_reads; }
+                         u64* d_topk_sum, void* slot, const BatchOut* out) {
+    PendingBatch nw = pending_batch(n_reads, out);
     nw.d_bases = d_bases; nw.d_offsets = d_offsets; nw.n_reads = n_reads; nw.n_bases = n_bases;
     nw.d_topk_idx = d_topk_idx; nw.d_topk_sum = d_topk_sum; nw.slot = slot;
     nw.pairable = st->coalesce >= 2;
@@ -3566,177 +3532,24 @@ static int enqueue_batch(skx_stream* st, const uint8_t* d_bases, const u64* d_of
     return SKX_OK;
 }
 
-// ---- consensus codes of a batch (skx_stream_bind_consensus)
-// every batch entry point begins by taking the binding: it is gone whatever becomes of the call
-static u32* take_consensus(skx_stream* st) {
-    u32* c = st->bound_cons;
-    st->bound_cons = nullptr;
-    return c;
-}
-// what a bound batch call needs (nothing has touched the device when it fails); device_rows: the caller's device row array of the
-// two _device entry points (a stream's own fallback rows are shared between the chains of enqueued batches)
-static int check_consensus(const char* who, const skx_stream* st, bool device_entry, const void* device_rows) {
-    if (!st->ref->d_codes) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but the reference has no genotype table", who);
-    if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but the stream was created with top_k=0", who);
-    if (device_entry && !device_rows) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but d_topk_idx is NULL", who);
-    return SKX_OK;
-}
-static size_t consensus_bytes(const skx_stream* st, u32 n_reads) { return (size_t)n_reads * st->ref->n_species * st->ref->n_features * 4; }
-
+// ---- bound outputs of a batch (skx_batch_out.hpp): four one-shot bindings kept in one record
 SKX_API int skx_stream_bind_consensus(skx_stream* st, uint32_t* codes_out) {
     if (!st || !codes_out) return fail(SKX_ERR_INVALID, "skx_stream_bind_consensus: NULL argument");
-    st->bound_cons = codes_out;
+    st->bound.cons = codes_out;
     return SKX_OK;
 }
-
-// ---- event list of a batch (skx_stream_bind_changes): one-shot like the consensus binding, taken by every batch entry point first
-static ChangeOut take_changes(skx_stream* st) {
-    const ChangeOut c = st->bound_chg;
-    st->bound_chg = ChangeOut{};
-    return c;
-}
-static int check_changes(const char* who, const skx_stream* st, const ChangeOut& c, bool device_entry, const void* device_rows) {
-    if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: an event list is bound but the stream was created with top_k=0", who);
-    if (device_entry && !device_rows) return fail(SKX_ERR_INVALID, "%s: an event list is bound but d_topk_idx is NULL", who);
-    if (c.codes && !st->ref->d_codes) return fail(SKX_ERR_INVALID, "%s: an event list of codes is bound but the reference has no genotype table", who);
-    return SKX_OK;
-}
-// device arrays of an event list for `cap` entries (push: the stream's, submit: a slot's).  They grow when a larger cap (or the first
-// list of codes) arrives; the caller has made sure that nothing queued still uses them.
-static int ensure_events(const skx_stream* st, ChangeOut& d, u32 cap, bool want_codes) {
-    if (d.n_events && d.cap >= cap && (!want_codes || d.ev_codes)) return SKX_OK;
-    (void)hipFree(d.n_events); (void)hipFree(d.ev_read); (void)hipFree(d.ev_idx); (void)hipFree(d.ev_sum); (void)hipFree(d.ev_codes);
-    const u32 keep = std::max(cap, d.cap);
-    d = ChangeOut{};
-    const size_t w_idx = (size_t)st->ref->n_species * st->top_k, w_codes = (size_t)st->ref->n_species * st->ref->n_features;
-    HIPCHK(hipMalloc(&d.n_events, 4));
-    HIPCHK(hipMalloc(&d.ev_read, (size_t)keep * 4));
-    HIPCHK(hipMalloc(&d.ev_idx, (size_t)keep * w_idx * 4));
-    HIPCHK(hipMalloc(&d.ev_sum, (size_t)keep * w_idx * 8));
-    if (w_codes) HIPCHK(hipMalloc(&d.ev_codes, (size_t)keep * w_codes * 4));
-    d.cap = keep;
-    return SKX_OK;
-}
-// what the kernels get: the device arrays `d` for the outputs the caller asked for in `want`
-static ChangeOut device_events(const ChangeOut& want, const ChangeOut& d) {
-    ChangeOut c;
-    c.cap = std::min(want.cap, d.cap);
-    c.n_events = d.n_events; c.ev_read = d.ev_read;
-    c.ev_idx = want.ev_idx ? d.ev_idx : nullptr;
-    c.ev_sum = want.ev_sum ? d.ev_sum : nullptr;
-    c.ev_codes = want.ev_codes ? d.ev_codes : nullptr;
-    c.codes = want.codes;
-    return c;
-}
-// the first min(n, cap) entries of the device arrays `d` to the caller's host arrays; nothing past them is touched
-static int deliver_events(const skx_stream* st, const ChangeOut& want, const ChangeOut& d, u32 n) {
-    *want.n_events = n;
-    const size_t m = std::min(n, std::min(want.cap, d.cap));
-    if (m == 0) return SKX_OK;
-    const size_t w_idx = (size_t)st->ref->n_species * st->top_k, w_codes = (size_t)st->ref->n_species * st->ref->n_features;
-    HIPCHK(hipMemcpy(want.ev_read, d.ev_read, m * 4, hipMemcpyDeviceToHost));
-    if (want.ev_idx) HIPCHK(hipMemcpy(want.ev_idx, d.ev_idx, m * w_idx * 4, hipMemcpyDeviceToHost));
-    if (want.ev_sum) HIPCHK(hipMemcpy(want.ev_sum, d.ev_sum, m * w_idx * 8, hipMemcpyDeviceToHost));
-    if (want.ev_codes) HIPCHK(hipMemcpy(want.ev_codes, d.ev_codes, m * w_codes * 4, hipMemcpyDeviceToHost));
-    return SKX_OK;
-}
-
 SKX_API int skx_stream_bind_changes(skx_stream* st, uint32_t cap, uint32_t* n_events, uint32_t* ev_read, uint32_t* ev_idx, uint64_t* ev_sum,
                                     uint32_t* ev_codes) {
     if (!st || !n_events || !ev_read) return fail(SKX_ERR_INVALID, "skx_stream_bind_changes: NULL argument");
     if (cap == 0) return fail(SKX_ERR_INVALID, "skx_stream_bind_changes: cap must be at least 1");
-    ChangeOut c;
-    c.cap = cap; c.n_events = n_events; c.ev_read = ev_read; c.ev_idx = ev_idx; c.ev_sum = reinterpret_cast<u64*>(ev_sum);
-    c.ev_codes = ev_codes; c.codes = ev_codes != nullptr;
-    st->bound_chg = c;
+    EventList c;
+    c.cap = cap; c.n_events = n_events; c.ev_read = ev_read; c.ev_idx = ev_idx; c.ev_sum = reinterpret_cast<u64*>(ev_sum); c.ev_codes = ev_codes;
+    st->bound.chg = c;
     return SKX_OK;
 }
-
-// ---- species call of a batch (skx_stream_bind_call, skx_stream_bind_call_changes): two one-shot bindings kept in one CallOut, taken
-// together by every batch entry point first
-static CallOut take_call(skx_stream* st) {
-    const CallOut c = st->bound_call;
-    st->bound_call = CallOut{};
-    return c;
-}
-static int check_call(const char* who, const skx_stream* st, const CallOut& c, bool device_entry, const void* device_idx, const void* device_sum) {
-    if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: a species call is bound but the stream was created with top_k=0", who);
-    if (c.wants_codes() && !st->ref->d_codes)
-        return fail(SKX_ERR_INVALID, "%s: a species call with codes is bound but the reference has no genotype table", who);
-    if (device_entry && (!device_idx || !device_sum))
-        return fail(SKX_ERR_INVALID, "%s: a species call is bound but d_topk_idx or d_topk_sum is NULL", who);
-    return SKX_OK;
-}
-// device arrays of a call for host-fed batches (push: the stream's, submit: a slot's): compact rows for max_reads reads, each allocated
-// when first asked for; event arrays for `cap` entries, which grow like ensure_events' (the caller has made sure nothing queued uses them)
-static int ensure_call(const skx_stream* st, CallOut& d, const CallOut& want) {
-    const size_t mr = st->max_reads, top = st->top_k, nf = st->ref->n_features;
-    if (want.on) {
-        if (!d.sp) HIPCHK(hipMalloc(&d.sp, mr * 4));
-        if (want.idx && !d.idx) HIPCHK(hipMalloc(&d.idx, mr * top * 4));
-        if (want.sum && !d.sum) HIPCHK(hipMalloc(&d.sum, mr * top * 8));
-        if (want.codes && !d.codes) HIPCHK(hipMalloc(&d.codes, mr * nf * 4));
-    }
-    const u32 cap = std::min<u32>(want.cap, st->max_reads);
-    if (cap == 0 || (d.n_events && d.cap >= cap && (!want.ev_codes || d.ev_codes))) return SKX_OK;
-    (void)hipFree(d.n_events); (void)hipFree(d.ev_read); (void)hipFree(d.ev_sp); (void)hipFree(d.ev_idx); (void)hipFree(d.ev_sum); (void)hipFree(d.ev_codes);
-    d.n_events = d.ev_read = d.ev_sp = d.ev_idx = d.ev_codes = nullptr; d.ev_sum = nullptr;
-    const size_t keep = std::max(cap, d.cap);
-    d.cap = 0;
-    HIPCHK(hipMalloc(&d.n_events, 4));
-    HIPCHK(hipMalloc(&d.ev_read, keep * 4));
-    HIPCHK(hipMalloc(&d.ev_sp, keep * 4));
-    HIPCHK(hipMalloc(&d.ev_idx, keep * top * 4));
-    HIPCHK(hipMalloc(&d.ev_sum, keep * top * 8));
-    if (nf) HIPCHK(hipMalloc(&d.ev_codes, keep * nf * 4));
-    d.cap = (u32)keep;
-    return SKX_OK;
-}
-// what the kernels get: the device arrays `d` for the outputs the caller asked for in `want`
-static CallOut device_call(const CallOut& want, const CallOut& d) {
-    CallOut c;
-    c.on = want.on;
-    if (want.on) {
-        c.sp = d.sp;
-        c.idx = want.idx ? d.idx : nullptr;
-        c.sum = want.sum ? d.sum : nullptr;
-        c.codes = want.codes ? d.codes : nullptr;
-    }
-    if (want.cap) {
-        c.cap = std::min(want.cap, d.cap);
-        c.n_events = d.n_events; c.ev_read = d.ev_read; c.ev_sp = d.ev_sp;
-        c.ev_idx = want.ev_idx ? d.ev_idx : nullptr;
-        c.ev_sum = want.ev_sum ? d.ev_sum : nullptr;
-        c.ev_codes = want.ev_codes ? d.ev_codes : nullptr;
-    }
-    return c;
-}
-// the compact rows of n_reads reads from the device arrays `d` to the caller's, queued on hs (page-locked or pageable host memory)
-static int copy_call_rows(const skx_stream* st, const CallOut& want, const CallOut& d, u32 n_reads, hipStream_t hs) {
-    if (!want.on) return SKX_OK;
-    const size_t n = n_reads, top = st->top_k, nf = st->ref->n_features;
-    HIPCHK(hipMemcpyAsync(want.sp, d.sp, n * 4, hipMemcpyDeviceToHost, hs));
-    if (want.idx) HIPCHK(hipMemcpyAsync(want.idx, d.idx, n * top * 4, hipMemcpyDeviceToHost, hs));
-    if (want.sum) HIPCHK(hipMemcpyAsync(want.sum, d.sum, n * top * 8, hipMemcpyDeviceToHost, hs));
-    if (want.codes) HIPCHK(hipMemcpyAsync(want.codes, d.codes, n * nf * 4, hipMemcpyDeviceToHost, hs));
-    return SKX_OK;
-}
-// the first min(n, cap) events of the device arrays `d` to the caller's host arrays; nothing past them is touched
-static int deliver_call_events(const skx_stream* st, const CallOut& want, const CallOut& d, u32 n) {
-    *want.n_events = n;
-    const size_t m = std::min(n, std::min(want.cap, d.cap)), top = st->top_k, nf = st->ref->n_features;
-    if (m == 0) return SKX_OK;
-    HIPCHK(hipMemcpy(want.ev_read, d.ev_read, m * 4, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(want.ev_sp, d.ev_sp, m * 4, hipMemcpyDeviceToHost));
-    if (want.ev_idx) HIPCHK(hipMemcpy(want.ev_idx, d.ev_idx, m * top * 4, hipMemcpyDeviceToHost));
-    if (want.ev_sum) HIPCHK(hipMemcpy(want.ev_sum, d.ev_sum, m * top * 8, hipMemcpyDeviceToHost));
-    if (want.ev_codes) HIPCHK(hipMemcpy(want.ev_codes, d.ev_codes, m * nf * 4, hipMemcpyDeviceToHost));
-    return SKX_OK;
-}
-
 SKX_API int skx_stream_bind_call(skx_stream* st, uint32_t* call_species, uint32_t* call_idx, uint64_t* call_sum, uint32_t* call_codes) {
     if (!st || !call_species) return fail(SKX_ERR_INVALID, "skx_stream_bind_call: NULL argument");
-    CallOut& c = st->bound_call;
+    skx::CallRows& c = st->bound.call;
     c.on = true; c.sp = call_species; c.idx = call_idx; c.sum = reinterpret_cast<u64*>(call_sum); c.codes = call_codes;
     return SKX_OK;
 }
@@ -3744,9 +3557,148 @@ SKX_API int skx_stream_bind_call_changes(skx_stream* st, uint32_t cap, uint32_t*
                                          uint32_t* ev_idx, uint64_t* ev_sum, uint32_t* ev_codes) {
     if (!st || !n_events || !ev_read || !ev_species) return fail(SKX_ERR_INVALID, "skx_stream_bind_call_changes: NULL argument");
     if (cap == 0) return fail(SKX_ERR_INVALID, "skx_stream_bind_call_changes: cap must be at least 1");
-    CallOut& c = st->bound_call;
+    EventList c;
     c.cap = cap; c.n_events = n_events; c.ev_read = ev_read; c.ev_sp = ev_species; c.ev_idx = ev_idx;
     c.ev_sum = reinterpret_cast<u64*>(ev_sum); c.ev_codes = ev_codes;
+    st->bound.call_ev = c;
+    return SKX_OK;
+}
+// every batch entry point begins by taking the record: it is gone whatever becomes of the call
+static BatchOut take_bound(skx_stream* st) {
+    const BatchOut o = st->bound;
+    st->bound = BatchOut{};
+    return o;
+}
+// what a bound batch call needs (nothing has touched the device when it fails); d_idx, d_sum: the caller's device row arrays of the
+// two _device entry points (a stream's own fallback rows are shared between the chains of enqueued batches)
+static int check_bound(const char* who, const skx_stream* st, const BatchOut& o, bool device_entry, const void* d_idx, const void* d_sum) {
+    const bool table = st->ref->d_codes != nullptr;
+    if (o.cons) {
+        if (!table) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but the reference has no genotype table", who);
+        if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but the stream was created with top_k=0", who);
+        if (device_entry && !d_idx) return fail(SKX_ERR_INVALID, "%s: a consensus output is bound but d_topk_idx is NULL", who);
+    }
+    if (o.chg.cap) {
+        if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: an event list is bound but the stream was created with top_k=0", who);
+        if (device_entry && !d_idx) return fail(SKX_ERR_INVALID, "%s: an event list is bound but d_topk_idx is NULL", who);
+        if (o.chg.codes() && !table) return fail(SKX_ERR_INVALID, "%s: an event list of codes is bound but the reference has no genotype table", who);
+    }
+    if (o.wants_call()) {
+        if (st->top_k == 0) return fail(SKX_ERR_INVALID, "%s: a species call is bound but the stream was created with top_k=0", who);
+        if ((o.call.codes || o.call_ev.codes()) && !table)
+            return fail(SKX_ERR_INVALID, "%s: a species call with codes is bound but the reference has no genotype table", who);
+        if (device_entry && (!d_idx || !d_sum))
+            return fail(SKX_ERR_INVALID, "%s: a species call is bound but d_topk_idx or d_topk_sum is NULL", who);
+    }
+    return SKX_OK;
+}
+// an empty batch has no events: host counts are written here, device counts by a memset queued on hs
+static int no_events(const BatchOut& o, bool device, hipStream_t hs) {
+    for (const EventList* ev : {&o.chg, &o.call_ev}) {
+        if (!ev->cap) continue;
+        if (device) HIPCHK(hipMemsetAsync(ev->n_events, 0, 4, hs));
+        else *ev->n_events = 0;
+    }
+    return SKX_OK;
+}
+static size_t consensus_bytes(const skx_stream* st, u32 n_reads) { return (size_t)n_reads * st->ref->n_species * st->ref->n_features * 4; }
+static skx::RowWidths chg_widths(const skx_stream* st) { return skx::change_widths(st->ref->n_species, st->top_k, st->ref->n_features); }
+static skx::RowWidths call_widths(const skx_stream* st) { return skx::call_widths(st->top_k, st->ref->n_features); }
+
+// ---- host-fed batches (push: the stream's holder, submit: a slot's): device copies, the way back
+// device arrays of an event list for `cap` entries.  They grow when a larger cap (or the first list of codes) arrives: everything is
+// freed and allocated again; the caller has made sure that nothing queued still uses them.
+static int ensure_events(EventList& d, u32 cap, bool want_codes, const skx::RowWidths& w, bool with_sp) {
+    if (d.n_events && d.cap >= cap && (!want_codes || d.ev_codes)) return SKX_OK;
+    const size_t keep = std::max(cap, d.cap);
+    free_events(d);
+    HIPCHK(hipMalloc(&d.n_events, 4));
+    HIPCHK(hipMalloc(&d.ev_read, keep * 4));
+    if (with_sp) HIPCHK(hipMalloc(&d.ev_sp, keep * 4));
+    HIPCHK(hipMalloc(&d.ev_idx, keep * w.idx * 4));
+    HIPCHK(hipMalloc(&d.ev_sum, keep * w.idx * 8));
+    if (w.codes) HIPCHK(hipMalloc(&d.ev_codes, keep * w.codes * 4));
+    d.cap = (u32)keep;
+    return SKX_OK;
+}
+// whatever of the holder `want` needs and is not there yet: codes and compact rows for max_reads reads, each allocated when first
+// asked for; event arrays for min(cap, max_reads) entries with the word their n_events travels back in
+static int ensure_out(const skx_stream* st, HostFedOut& h, const BatchOut& want) {
+    const size_t mr = st->max_reads;
+    const skx::RowWidths kw = call_widths(st);
+    if (want.wants_vote()) SKXCHK(lazy_alloc(h.d.cons, consensus_bytes(st, st->max_reads)));
+    if (want.call.on) {
+        SKXCHK(lazy_alloc(h.d.call.sp, mr * 4));
+        if (want.call.idx) SKXCHK(lazy_alloc(h.d.call.idx, mr * kw.idx * 4));
+        if (want.call.sum) SKXCHK(lazy_alloc(h.d.call.sum, mr * kw.idx * 8));
+        if (want.call.codes) SKXCHK(lazy_alloc(h.d.call.codes, mr * kw.codes * 4));
+    }
+    const EventList* wants[2] = {&want.chg, &want.call_ev};
+    EventList* have[2] = {&h.d.chg, &h.d.call_ev};
+    for (int i = 0; i < 2; ++i) {
+        if (!wants[i]->cap) continue;
+        SKXCHK(ensure_events(*have[i], std::min(wants[i]->cap, st->max_reads), wants[i]->codes(), i ? kw : chg_widths(st), i == 1));
+        if (!h.h_n[i]) HIPCHK(hipHostMalloc((void**)&h.h_n[i], 4, hipHostMallocDefault));
+    }
+    return SKX_OK;
+}
+// behind the batch's ranking on hs: codes, compact rows and the two n_events to the host (the events follow once n_events is known)
+static int queue_out_copies(const skx_stream* st, const BatchOut& want, const HostFedOut& h, u32 n_reads, hipStream_t hs) {
+    const size_t n = n_reads;
+    const skx::RowWidths kw = call_widths(st);
+    if (want.cons) HIPCHK(hipMemcpyAsync(want.cons, h.d.cons, consensus_bytes(st, n_reads), hipMemcpyDeviceToHost, hs));
+    if (want.chg.cap) HIPCHK(hipMemcpyAsync(h.h_n[0], h.d.chg.n_events, 4, hipMemcpyDeviceToHost, hs));
+    if (want.call.on) {
+        HIPCHK(hipMemcpyAsync(want.call.sp, h.d.call.sp, n * 4, hipMemcpyDeviceToHost, hs));
+        if (want.call.idx) HIPCHK(hipMemcpyAsync(want.call.idx, h.d.call.idx, n * kw.idx * 4, hipMemcpyDeviceToHost, hs));
+        if (want.call.sum) HIPCHK(hipMemcpyAsync(want.call.sum, h.d.call.sum, n * kw.idx * 8, hipMemcpyDeviceToHost, hs));
+        if (want.call.codes) HIPCHK(hipMemcpyAsync(want.call.codes, h.d.call.codes, n * kw.codes * 4, hipMemcpyDeviceToHost, hs));
+    }
+    if (want.call_ev.cap) HIPCHK(hipMemcpyAsync(h.h_n[1], h.d.call_ev.n_events, 4, hipMemcpyDeviceToHost, hs));
+    return SKX_OK;
+}
+// the first min(n, cap) entries of the device arrays `d` to the caller's host arrays; nothing past them is touched
+static int deliver_events(const EventList& want, const EventList& d, u32 n, const skx::RowWidths& w) {
+    *want.n_events = n;
+    const size_t m = std::min(n, std::min(want.cap, d.cap));
+    if (m == 0) return SKX_OK;
+    HIPCHK(hipMemcpy(want.ev_read, d.ev_read, m * 4, hipMemcpyDeviceToHost));
+    if (want.ev_sp) HIPCHK(hipMemcpy(want.ev_sp, d.ev_sp, m * 4, hipMemcpyDeviceToHost));
+    if (want.ev_idx) HIPCHK(hipMemcpy(want.ev_idx, d.ev_idx, m * w.idx * 4, hipMemcpyDeviceToHost));
+    if (want.ev_sum) HIPCHK(hipMemcpy(want.ev_sum, d.ev_sum, m * w.idx * 8, hipMemcpyDeviceToHost));
+    if (want.ev_codes) HIPCHK(hipMemcpy(want.ev_codes, d.ev_codes, m * w.codes * 4, hipMemcpyDeviceToHost));
+    return SKX_OK;
+}
+// the batch is through and queue_out_copies' words have landed: both lists to the caller's arrays
+static int deliver_out(const skx_stream* st, const BatchOut& want, const HostFedOut& h) {
+    if (want.chg.cap) SKXCHK(deliver_events(want.chg, h.d.chg, *static_cast<volatile u32*>(h.h_n[0]), chg_widths(st)));
+    if (want.call_ev.cap) SKXCHK(deliver_events(want.call_ev, h.d.call_ev, *static_cast<volatile u32*>(h.h_n[1]), call_widths(st)));
+    return SKX_OK;
+}
+// what skx_stream_push and skx_stream_submit ask of a batch of at least one read
+static int check_host_batch(const skx_stream* st, const uint8_t* bases, const uint64_t* offsets, u32 n_reads, const void* topk_idx,
+                            const void* topk_sum, u64* n_bases_out) {
+    if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
+    for (u32 r = 0; r < n_reads; ++r)
+        if (offsets[r + 1] < offsets[r]) return fail(SKX_ERR_INVALID, "offsets not monotonic at read %u", r);
+    const u64 n_bases = offsets[n_reads] - offsets[0];
+    if (n_bases > st->max_bases) return fail(SKX_ERR_CAPACITY, "batch has %llu bases > max_batch_bases=%llu",
+                                             (unsigned long long)n_bases, (unsigned long long)st->max_bases);
+    if (n_bases && !bases) return fail(SKX_ERR_INVALID, "bases is NULL");
+    if ((topk_idx || topk_sum) && st->top_k == 0) return fail(SKX_ERR_INVALID, "stream was created with top_k=0");
+    *n_bases_out = n_bases;
+    return SKX_OK;
+}
+// the batch to the device on hs: its offsets rebased to 0 through the page-locked h_offsets (packed input: to the first byte that
+// holds a base of the batch), then its bytes
+static int copy_host_batch(const skx_stream* st, const uint8_t* bases, const uint64_t* offsets, u32 n_reads, u64* h_offsets, u64* d_offsets,
+                           uint8_t* d_bases, hipStream_t hs) {
+    const u64 base0 = offsets[0], n_bases = offsets[n_reads] - base0;
+    const u64 byte0 = st->packed ? base0 >> 1 : base0, rebase = st->packed ? byte0 * 2 : base0;
+    const u64 n_bytes = st->packed ? ((offsets[n_reads] + 1) >> 1) - byte0 : n_bases;
+    for (u32 r = 0; r <= n_reads; ++r) h_offsets[r] = offsets[r] - rebase;
+    HIPCHK(hipMemcpyAsync(d_offsets, h_offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, hs));
+    if (n_bases) HIPCHK(hipMemcpyAsync(d_bases, bases + byte0, n_bytes, hipMemcpyHostToDevice, hs));
     return SKX_OK;
 }
 
@@ -3754,64 +3706,28 @@ SKX_API int skx_stream_push(skx_stream* st, const uint8_t* bases, const uint64_t
                             uint32_t* topk_idx, uint64_t* topk_sum, uint32_t* per_read_shared, uint64_t* sketches,
                             uint32_t* sketch_len) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL argument");
-    u32* const cons = take_consensus(st);
-    const ChangeOut chg = take_changes(st);
-    const CallOut call = take_call(st);
+    const BatchOut out = take_bound(st);
     if (!offsets) return fail(SKX_ERR_INVALID, "NULL argument");
-    if (cons) SKXCHK(check_consensus("skx_stream_push", st, false, nullptr));
-    if (chg.cap) SKXCHK(check_changes("skx_stream_push", st, chg, false, nullptr));
-    if (call.any()) SKXCHK(check_call("skx_stream_push", st, call, false, nullptr, nullptr));
-    if (n_reads == 0) {
-        if (chg.cap) *chg.n_events = 0;
-        if (call.cap) *call.n_events = 0;
-        return SKX_OK;
-    }
-    if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
-    for (u32 r = 0; r < n_reads; ++r)
-        if (offsets[r + 1] < offsets[r]) return fail(SKX_ERR_INVALID, "offsets not monotonic at read %u", r);
-    const u64 base0 = offsets[0], n_bases = offsets[n_reads] - base0;
-    if (n_bases > st->max_bases) return fail(SKX_ERR_CAPACITY, "batch has %llu bases > max_batch_bases=%llu",
-                                             (unsigned long long)n_bases, (unsigned long long)st->max_bases);
-    if (n_bases && !bases) return fail(SKX_ERR_INVALID, "bases is NULL");
-    if ((topk_idx || topk_sum) && st->top_k == 0) return fail(SKX_ERR_INVALID, "stream was created with top_k=0");
+    SKXCHK(check_bound("skx_stream_push", st, out, false, nullptr, nullptr));
+    if (n_reads == 0) return no_events(out, false, nullptr);
+    u64 n_bases = 0;
+    SKXCHK(check_host_batch(st, bases, offsets, n_reads, topk_idx, topk_sum, &n_bases));
     SKXCHK(use_device(st->device));
-    const bool vote = cons || chg.codes || call.wants_codes();  // (an event list of codes and a call with codes vote into the same scratch)
-    if (vote && !st->d_cons) HIPCHK(hipMalloc(&st->d_cons, consensus_bytes(st, st->max_reads)));
     SKXCHK(flush_pending(st));
-    ChangeOut d_chg;
-    if (chg.cap) {  // (pushes are synchronous: nothing queued uses the stream's event arrays)
-        SKXCHK(ensure_events(st, st->d_ev, std::min(chg.cap, st->max_reads), chg.codes));
-        d_chg = device_events(chg, st->d_ev);
-    }
-    CallOut d_call;
-    if (call.any()) {
-        SKXCHK(ensure_call(st, st->d_call, call));
-        d_call = device_call(call, st->d_call);
-    }
+    SKXCHK(ensure_out(st, st->push_out, out));  // (pushes are synchronous: nothing queued uses the stream's copies)
+    const BatchOut d_out = skx::device_view(out, st->push_out.d);
     hipStream_t hs = st->hs0;
-    // rebase offsets to 0 on the way in (packed input: to the first byte that holds a base of the batch)
-    const u64 byte0 = st->packed ? base0 >> 1 : base0, rebase = st->packed ? byte0 * 2 : base0;
-    const u64 n_bytes = st->packed ? ((offsets[n_reads] + 1) >> 1) - byte0 : n_bases;
-    for (u32 r = 0; r <= n_reads; ++r) st->h_offsets[r] = offsets[r] - rebase;
-    HIPCHK(hipMemcpyAsync(st->d_offsets, st->h_offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, hs));
-    if (n_bases) HIPCHK(hipMemcpyAsync(st->d_bases, bases + byte0, n_bytes, hipMemcpyHostToDevice, hs));
+    SKXCHK(copy_host_batch(st, bases, offsets, n_reads, st->h_offsets, st->d_offsets, st->d_bases, hs));
     SKXCHK(process_batch(st, st->d_bases, st->d_offsets, n_reads, n_bases, st->d_topk_idx, st->d_topk_sum,
-                         per_read_shared, reinterpret_cast<u64*>(sketches), sketch_len, vote ? st->d_cons : nullptr, chg.cap ? &d_chg : nullptr,
-                         call.any() ? &d_call : nullptr));
+                         per_read_shared, reinterpret_cast<u64*>(sketches), sketch_len, out.any() ? &d_out : nullptr));
     SKXCHK(queue_chains(st, true));    // the ranking of the batch's last pass (waits for its candidates)
     HIPCHK(hipStreamSynchronize(hs));  // sketch copies (first stream)
     const size_t rows = (size_t)n_reads * st->ref->n_species * st->top_k;
     if (topk_idx) HIPCHK(hipMemcpyAsync(topk_idx, st->d_topk_idx, rows * 4, hipMemcpyDeviceToHost, st->hs2));
     if (topk_sum) HIPCHK(hipMemcpyAsync(topk_sum, st->d_topk_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
-    if (cons) HIPCHK(hipMemcpyAsync(cons, st->d_cons, consensus_bytes(st, n_reads), hipMemcpyDeviceToHost, st->hs2));
-    u32 n_ev = 0;
-    if (chg.cap) HIPCHK(hipMemcpyAsync(&n_ev, st->d_ev.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
-    u32 n_cev = 0;
-    SKXCHK(copy_call_rows(st, call, st->d_call, n_reads, st->hs2));
-    if (call.cap) HIPCHK(hipMemcpyAsync(&n_cev, st->d_call.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
+    SKXCHK(queue_out_copies(st, out, st->push_out, n_reads, st->hs2));
     HIPCHK(hipStreamSynchronize(st->hs2));  // the rows are written by the back half
-    if (chg.cap) SKXCHK(deliver_events(st, chg, st->d_ev, n_ev));
-    if (call.cap) SKXCHK(deliver_call_events(st, call, st->d_call, n_cev));
+    SKXCHK(deliver_out(st, out, st->push_out));
     if (st->profiling) collect_spans(st);
     return SKX_OK;
 }
@@ -3828,45 +3744,32 @@ static int check_device_batch(skx_stream* st, const uint8_t* d_bases, const uint
 }
 SKX_API int skx_stream_push_device(skx_stream* st, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
                                    uint64_t n_bases, uint32_t* d_topk_idx, uint64_t* d_topk_sum) {
-    u32* const cons = st ? take_consensus(st) : nullptr;
-    const ChangeOut chg = st ? take_changes(st) : ChangeOut{};
-    const CallOut call = st ? take_call(st) : CallOut{};
+    const BatchOut out = st ? take_bound(st) : BatchOut{};
     SKXCHK(check_device_batch(st, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum));
-    if (cons) SKXCHK(check_consensus("skx_stream_push_device", st, true, d_topk_idx));
-    if (chg.cap) SKXCHK(check_changes("skx_stream_push_device", st, chg, true, d_topk_idx));
-    if (call.any()) SKXCHK(check_call("skx_stream_push_device", st, call, true, d_topk_idx, d_topk_sum));
+    SKXCHK(check_bound("skx_stream_push_device", st, out, true, d_topk_idx, d_topk_sum));
     SKXCHK(use_device(st->device));
     if (n_reads == 0) {
         SKXCHK(flush_pending(st));
-        if (chg.cap) HIPCHK(hipMemsetAsync(chg.n_events, 0, 4, st->hs2));
-        if (call.cap) HIPCHK(hipMemsetAsync(call.n_events, 0, 4, st->hs2));
-        return SKX_OK;
+        return no_events(out, true, st->hs2);
     }
     u32* ti = d_topk_idx ? d_topk_idx : st->d_topk_idx;
     u64* ts = d_topk_sum ? reinterpret_cast<u64*>(d_topk_sum) : st->d_topk_sum;
-    return process_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, nullptr, nullptr, cons,
-                         chg.cap ? &chg : nullptr, call.any() ? &call : nullptr);
+    return process_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, nullptr, nullptr,
+                         out.any() ? &out : nullptr);
 }
 SKX_API int skx_stream_enqueue_device(skx_stream* st, const uint8_t* d_bases, const uint64_t* d_offsets, uint32_t n_reads,
                                       uint64_t n_bases, uint32_t* d_topk_idx, uint64_t* d_topk_sum) {
-    u32* const cons = st ? take_consensus(st) : nullptr;
-    const ChangeOut chg = st ? take_changes(st) : ChangeOut{};
-    const CallOut call = st ? take_call(st) : CallOut{};
+    const BatchOut out = st ? take_bound(st) : BatchOut{};
     SKXCHK(check_device_batch(st, d_bases, d_offsets, n_reads, n_bases, d_topk_idx, d_topk_sum));
-    if (cons) SKXCHK(check_consensus("skx_stream_enqueue_device", st, true, d_topk_idx));
-    if (chg.cap) SKXCHK(check_changes("skx_stream_enqueue_device", st, chg, true, d_topk_idx));
-    if (call.any()) SKXCHK(check_call("skx_stream_enqueue_device", st, call, true, d_topk_idx, d_topk_sum));
+    SKXCHK(check_bound("skx_stream_enqueue_device", st, out, true, d_topk_idx, d_topk_sum));
     if (n_reads == 0) {
-        if (chg.cap || call.cap) SKXCHK(use_device(st->device));
-        if (chg.cap) HIPCHK(hipMemsetAsync(chg.n_events, 0, 4, st->hs2));
-        if (call.cap) HIPCHK(hipMemsetAsync(call.n_events, 0, 4, st->hs2));
-        return SKX_OK;
+        if (out.chg.cap || out.call_ev.cap) SKXCHK(use_device(st->device));
+        return no_events(out, true, st->hs2);
     }
     SKXCHK(use_device(st->device));
     u32* ti = d_topk_idx ? d_topk_idx : st->d_topk_idx;
     u64* ts = d_topk_sum ? reinterpret_cast<u64*>(d_topk_sum) : st->d_topk_sum;
-    return enqueue_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, cons, chg.cap ? &chg : nullptr,
-                         call.any() ? &call : nullptr);
+    return enqueue_batch(st, d_bases, reinterpret_cast<const u64*>(d_offsets), n_reads, n_bases, ti, ts, nullptr, out.any() ? &out : nullptr);
 }
 SKX_API int skx_stream_flush(skx_stream* st) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
@@ -3882,10 +3785,7 @@ static int staged_rows(skx_stream* st, void* slot) {
     const size_t rows = (size_t)sl.n_reads * st->ref->n_species * st->top_k;
     if (sl.out_idx) HIPCHK(hipMemcpyAsync(sl.out_idx, sl.d_rows_idx, rows * 4, hipMemcpyDeviceToHost, st->hs2));
     if (sl.out_sum) HIPCHK(hipMemcpyAsync(sl.out_sum, sl.d_rows_sum, rows * 8, hipMemcpyDeviceToHost, st->hs2));
-    if (sl.out_cons) HIPCHK(hipMemcpyAsync(sl.out_cons, sl.d_cons, consensus_bytes(st, sl.n_reads), hipMemcpyDeviceToHost, st->hs2));
-    if (sl.out_chg.cap) HIPCHK(hipMemcpyAsync(sl.h_ev_n, sl.d_ev.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
-    SKXCHK(copy_call_rows(st, sl.out_call, sl.d_call, sl.n_reads, st->hs2));
-    if (sl.out_call.cap) HIPCHK(hipMemcpyAsync(sl.h_cev_n, sl.d_call.n_events, 4, hipMemcpyDeviceToHost, st->hs2));
+    SKXCHK(queue_out_copies(st, sl.out, sl.dev, sl.n_reads, st->hs2));
     HIPCHK(hipEventRecord(sl.ev_done, st->hs2));
     sl.in_flight = true;
     return SKX_OK;
@@ -3894,13 +3794,9 @@ static int staged_rows(skx_stream* st, void* slot) {
 // known only now, and nothing past min(n_events, cap) may be written
 static int staged_landed(skx_stream* st, skx_stream::Staged& sl) {
     sl.in_flight = false;
-    const ChangeOut want = sl.out_chg;
-    const CallOut want_call = sl.out_call;
-    sl.out_chg = ChangeOut{};
-    sl.out_call = CallOut{};
-    if (want.cap) SKXCHK(deliver_events(st, want, sl.d_ev, *static_cast<volatile u32*>(sl.h_ev_n)));
-    if (want_call.cap) SKXCHK(deliver_call_events(st, want_call, sl.d_call, *static_cast<volatile u32*>(sl.h_cev_n)));
-    return SKX_OK;
+    const BatchOut want = sl.out;
+    sl.out = BatchOut{};
+    return deliver_out(st, want, sl.dev);
 }
 static void staged_drop(void* slot) {
     if (slot) static_cast<skx_stream::Staged*>(slot)->dropped = true;
@@ -3910,13 +3806,8 @@ static int staged_process(skx_stream* st, skx_stream::Staged& sl) {
     if (!sl.pending) return SKX_OK;
     sl.pending = false;
     HIPCHK(hipStreamWaitEvent(st->hs0, sl.ev_copy, 0));  // the batch must have landed before the sketcher reads it
-    ChangeOut d_chg;
-    if (sl.out_chg.cap) d_chg = device_events(sl.out_chg, sl.d_ev);
-    CallOut d_call;
-    if (sl.out_call.any()) d_call = device_call(sl.out_call, sl.d_call);
-    return enqueue_batch(st, sl.d_bases, sl.d_offsets, sl.n_reads, sl.n_bases, sl.d_rows_idx, sl.d_rows_sum, &sl,
-                         (sl.out_cons || sl.out_chg.codes || sl.out_call.wants_codes()) ? sl.d_cons : nullptr, sl.out_chg.cap ? &d_chg : nullptr,
-                         sl.out_call.any() ? &d_call : nullptr);
+    const BatchOut d_out = skx::device_view(sl.out, sl.dev.d);
+    return enqueue_batch(st, sl.d_bases, sl.d_offsets, sl.n_reads, sl.n_bases, sl.d_rows_idx, sl.d_rows_sum, &sl, sl.out.any() ? &d_out : nullptr);
 }
 // ... until its rows are on the host
 static int staged_finish(skx_stream* st, skx_stream::Staged& sl) {
@@ -3935,22 +3826,12 @@ static int staged_finish(skx_stream* st, skx_stream::Staged& sl) {
 SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64_t* offsets, uint32_t n_reads,
                               uint32_t* topk_idx, uint64_t* topk_sum, uint64_t* ticket) {
     if (!st) return fail(SKX_ERR_INVALID, "NULL argument");
-    u32* const cons = take_consensus(st);
-    const ChangeOut chg = take_changes(st);
-    const CallOut call = take_call(st);
+    const BatchOut out = take_bound(st);
     if (!offsets) return fail(SKX_ERR_INVALID, "NULL argument");
-    if (cons) SKXCHK(check_consensus("skx_stream_submit", st, false, nullptr));
-    if (chg.cap) SKXCHK(check_changes("skx_stream_submit", st, chg, false, nullptr));
-    if (call.any()) SKXCHK(check_call("skx_stream_submit", st, call, false, nullptr, nullptr));
+    SKXCHK(check_bound("skx_stream_submit", st, out, false, nullptr, nullptr));
     if (n_reads == 0) return fail(SKX_ERR_INVALID, "empty batch");
-    if (n_reads > st->max_reads) return fail(SKX_ERR_CAPACITY, "n_reads=%u exceeds max_batch_reads=%u", n_reads, st->max_reads);
-    for (u32 r = 0; r < n_reads; ++r)
-        if (offsets[r + 1] < offsets[r]) return fail(SKX_ERR_INVALID, "offsets not monotonic at read %u", r);
-    const u64 base0 = offsets[0], n_bases = offsets[n_reads] - base0;
-    if (n_bases > st->max_bases) return fail(SKX_ERR_CAPACITY, "batch has %llu bases > max_batch_bases=%llu",
-                                             (unsigned long long)n_bases, (unsigned long long)st->max_bases);
-    if (n_bases && !bases) return fail(SKX_ERR_INVALID, "bases is NULL");
-    if ((topk_idx || topk_sum) && st->top_k == 0) return fail(SKX_ERR_INVALID, "stream was created with top_k=0");
+    u64 n_bases = 0;
+    SKXCHK(check_host_batch(st, bases, offsets, n_reads, topk_idx, topk_sum, &n_bases));
     SKXCHK(use_device(st->device));
     if (!st->hs_copy) {  // first use: copy stream + the staging slots
         HIPCHK(hipStreamCreateWithFlags(&st->hs_copy, hipStreamNonBlocking));
@@ -3968,9 +3849,8 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
             HIPCHK(hipEventCreateWithFlags(&sl.ev_done, hipEventDisableTiming));
         }
     }
-    if (cons)  // (the first bound submit: a device copy of the codes for every slot)
-        for (u32 si = 0; si < st->n_slots; ++si)
-            if (!st->slot[si].d_cons) HIPCHK(hipMalloc(&st->slot[si].d_cons, consensus_bytes(st, st->max_reads)));
+    if (out.cons)  // (the first submit with a consensus output: a device copy of the codes for every slot)
+        for (u32 si = 0; si < st->n_slots; ++si) SKXCHK(lazy_alloc(st->slot[si].dev.d.cons, consensus_bytes(st, st->max_reads)));
     const u32 ns = st->n_slots;
     skx_stream::Staged& sl = st->slot[st->next_ticket % ns];
     skx_stream::Staged& other = st->slot[(st->next_ticket + ns - 1) % ns];  // (the previous ticket's)
@@ -3980,26 +3860,11 @@ SKX_API int skx_stream_submit(skx_stream* st, const uint8_t* bases, const uint64
     // engine stood still whenever the host waited in (3), and a stream of 32 768-read batches took 1.4 ms per batch where its
     // copies take 0.45 ms.
     SKXCHK(staged_finish(st, sl));
-    if (chg.cap) {  // (the slot is idle now: its event arrays may grow)
-        SKXCHK(ensure_events(st, sl.d_ev, std::min(chg.cap, st->max_reads), chg.codes));
-        if (!sl.h_ev_n) HIPCHK(hipHostMalloc((void**)&sl.h_ev_n, 4, hipHostMallocDefault));
-        if (chg.codes && !sl.d_cons) HIPCHK(hipMalloc(&sl.d_cons, consensus_bytes(st, st->max_reads)));
-    }
-    if (call.any()) {  // (likewise: the slot's compact rows and its call events)
-        SKXCHK(ensure_call(st, sl.d_call, call));
-        if (call.cap && !sl.h_cev_n) HIPCHK(hipHostMalloc((void**)&sl.h_cev_n, 4, hipHostMallocDefault));
-        if (call.wants_codes() && !sl.d_cons) HIPCHK(hipMalloc(&sl.d_cons, consensus_bytes(st, st->max_reads)));
-    }
-    const u64 byte0 = st->packed ? base0 >> 1 : base0, rebase = st->packed ? byte0 * 2 : base0;
-    const u64 n_bytes = st->packed ? ((offsets[n_reads] + 1) >> 1) - byte0 : n_bases;
-    for (u32 r = 0; r <= n_reads; ++r) sl.h_offsets[r] = offsets[r] - rebase;
-    HIPCHK(hipMemcpyAsync(sl.d_offsets, sl.h_offsets, ((size_t)n_reads + 1) * 8, hipMemcpyHostToDevice, st->hs_copy));
-    if (n_bases) HIPCHK(hipMemcpyAsync(sl.d_bases, bases + byte0, n_bytes, hipMemcpyHostToDevice, st->hs_copy));
+    SKXCHK(ensure_out(st, sl.dev, out));  // (the slot is idle now: its event arrays may grow)
+    SKXCHK(copy_host_batch(st, bases, offsets, n_reads, sl.h_offsets, sl.d_offsets, sl.d_bases, st->hs_copy));
     HIPCHK(hipEventRecord(sl.ev_copy, st->hs_copy));
     sl.pending = true; sl.dropped = false; sl.n_reads = n_reads; sl.n_bases = n_bases; sl.out_idx = topk_idx; sl.out_sum = reinterpret_cast<u64*>(topk_sum);
-    sl.out_cons = cons;
-    sl.out_chg = chg;
-    sl.out_call = call;
+    sl.out = out;
     sl.ticket = st->next_ticket;
     if (ticket) *ticket = st->next_ticket;
     st->next_ticket += 1;

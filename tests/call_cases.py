@@ -28,7 +28,8 @@ def call_changes_ref(species, part):
     if n == 0:
         return np.zeros(0, np.int64)
     flag = np.ones(n, bool)
-    flag[1:] = (species[1:] != species[:-1]) | (part[1:] != part[:-1]).reshape(n - 1, -1).any(axis=1)
+    if n > 1:  # (reshape(0, -1) cannot size an empty array)
+        flag[1:] = (species[1:] != species[:-1]) | (part[1:] != part[:-1]).reshape(n - 1, -1).any(axis=1)
     return np.flatnonzero(flag)
 
 

@@ -29,6 +29,8 @@
  *                             say which of the resident species the sample is after every read, with that species' rows alone
  *   skx_stream_enable_coverage / skx_stream_coverage[_rows|_rank] <- no counterpart: the reference keeps sums only; these say how many of
  *                             a genome's own sketch hashes the reads have shared at least once (containment, as `mash screen` reports it)
+ *   skx_stream_winners[_rows|_rank] <- no counterpart: the breadth with every seen hash credited to ONE genome, the best of its
+ *                             holders (`mash screen -w`): a clone tree's thousands of copies of one lineage stop outranking a second strain
  *   skx_stream_enable_depth / skx_stream_depth[_rows|_count|_export|_import] <- no counterpart: how OFTEN each of a genome's hashes was
  *                             shared (the median multiplicity of `mash screen`), and the counters as portable (hash, count) pairs
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
@@ -447,6 +449,34 @@ int skx_stream_enable_coverage(skx_stream *st);
 int skx_stream_coverage(skx_stream *st, uint32_t *covered);
 int skx_stream_coverage_rows(skx_stream *st, const uint32_t *genomes, uint32_t n, uint32_t *covered);
 int skx_stream_coverage_rank(skx_stream *st, uint32_t top_k, uint32_t *idx, uint32_t *covered);
+/*
+ * Winner-takes-all breadth (`mash screen -w`; one round, as Mash does).  covered[g] credits a seen hash to every genome that holds it, so
+ * in a clone tree the top of a ranking by covered is one lineage listed many times.  Here every seen hash is credited once:
+ *   order      one global order over all genomes of the resident reference, all species together.  g precedes h when
+ *              covered[g] * max(len[h], 1) > covered[h] * max(len[g], 1) (the larger containment, exact, in 64 bits; len = col_len, lifted
+ *              hashes included); when the products are equal, covered[g] > covered[h]; when those are equal too, g < h (global indices)
+ *   winner(x)  for every seen reference hash x, lifted ones included: the first genome in this order among the genomes that hold x
+ *   won[g]     = number of seen hashes of g's column whose winner is g
+ * Integer, exact, independent of how the reads were cut into batches.  won[g] <= covered[g]; the sum of won over all genomes is the
+ * number of distinct seen hashes some genome holds (skx_stream_depth_count on a stream with depth); the first genome of the order has
+ * won == covered; a reference whose genomes share nothing has won == covered everywhere.  The order comes from the plain covered and is
+ * not iterated.
+ * Nothing is enabled separately: the queries need skx_stream_enable_coverage, recompute everything from the seen set (so skx_stream_reset,
+ * _table_add, _allreduce and _depth_import need no special handling), and a stream that never asks allocates and launches nothing for
+ * them.  The first query allocates its scratch -- one uint32_t per bit of the seen set, two per padded genome --, skx_stream_destroy frees
+ * it.  A query flushes pending batches, counts the whole table, brings the counts to the host for ONE sort of n_genomes keys, sends the
+ * ranks back, and walks the matrix twice more: every holder of a hash can be its winner, so the marking walk always covers the whole
+ * table, whatever is asked for; only the final count is restricted to the genomes of a list.
+ *   skx_stream_winners       covered / won [n_genomes] (host), species one after the other; either may be NULL
+ *   skx_stream_winners_rows  the same for the global genome indices genomes[0..n) (any order, repeats allowed); n == 0: SKX_OK
+ *   skx_stream_winners_rank  per species the first top_k of (won desc, index asc): idx / won [n_species][top_k], indices local to the
+ *                            species; top_k as in skx_stream_coverage_rank
+ * SKX_ERR_INVALID: a stream that never enabled coverage; and, before the device is touched, a NULL stream, list or (_rank) output, an
+ * index >= n_genomes (the outputs are untouched), top_k out of range.
+ */
+int skx_stream_winners(skx_stream *st, uint32_t *covered, uint32_t *won);
+int skx_stream_winners_rows(skx_stream *st, const uint32_t *genomes, uint32_t n, uint32_t *covered, uint32_t *won);
+int skx_stream_winners_rank(skx_stream *st, uint32_t top_k, uint32_t *idx, uint32_t *won);
 /*
  * Depth of a stream (no counterpart in the reference binary; the median-multiplicity column of `mash screen`).  Breadth says whether a
  * genome is there, not how deep: a containment of 0.95 reads the same from 40 reads and from 4 million, and a contaminant seen once per

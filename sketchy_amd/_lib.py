@@ -72,6 +72,9 @@ SYMBOLS = [
     ("skx_stream_coverage", _i, [_vp, _vp]),
     ("skx_stream_coverage_rows", _i, [_vp, _vp, _u32, _vp]),
     ("skx_stream_coverage_rank", _i, [_vp, _u32, _vp, _vp]),
+    ("skx_stream_winners", _i, [_vp, _vp, _vp]),
+    ("skx_stream_winners_rows", _i, [_vp, _vp, _u32, _vp, _vp]),
+    ("skx_stream_winners_rank", _i, [_vp, _u32, _vp, _vp]),
     ("skx_stream_enable_depth", _i, [_vp]),
     ("skx_stream_depth", _i, [_vp, _vp, _vp, _vp]),
     ("skx_stream_depth_rows", _i, [_vp, _vp, _u32, _vp, _vp, _vp]),

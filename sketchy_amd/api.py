@@ -486,6 +486,29 @@ class SumOfSharedHashes:
         _lib.check(_lib.load().skx_stream_coverage_rank(self._h, top, _p(idx), _p(cov)))
         return idx, cov
 
+    def winners(self):
+        """(covered, won), each uint32 [n_genomes]: won[g] = seen hashes of g's column credited to g alone -- every seen hash goes to the
+        first of its holders in the global order (containment, then covered, then index): skx_stream_winners, `mash screen -w`."""
+        n = self.ref.n_genomes
+        cov, won = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        _lib.check(_lib.load().skx_stream_winners(self._h, _p(cov), _p(won)))
+        return cov, won
+
+    def winners_rows(self, genomes):
+        """The same for a list of global genome indices (any order, repeats allowed)."""
+        genomes = np.ascontiguousarray(genomes, np.uint32).reshape(-1)
+        cov, won = np.zeros(len(genomes), np.uint32), np.zeros(len(genomes), np.uint32)
+        _lib.check(_lib.load().skx_stream_winners_rows(self._h, _p(genomes), len(genomes), _p(cov), _p(won)))
+        return cov, won
+
+    def winners_rank(self, top):
+        """Per species the first `top` genomes of (won desc, index asc): (idx, won), each [n_species, top], indices local to the species."""
+        top = int(top)
+        shape = (self.ref.n_species, max(top, 0))
+        idx, won = np.zeros(shape, np.uint32), np.zeros(shape, np.uint32)
+        _lib.check(_lib.load().skx_stream_winners_rank(self._h, top, _p(idx), _p(won)))
+        return idx, won
+
     def enable_depth(self):
         """Give the stream one saturating counter per reference hash (skx_stream_enable_depth; enables coverage too): before the first
         read, or after reset()."""

@@ -31,6 +31,7 @@
 #include "skx_batch_out.hpp"
 #include "skx_common.hpp"
 #include "skx_genome_groups.hpp"
+#include "skx_winner_order.hpp"
 #include "skx_kernels.hpp"
 
 using skx::BatchOut;
@@ -257,6 +258,7 @@ struct skx_ref {
     u32 max_species = 0;                     // largest species (more genomes than a compact ranking takes: a fresh table cannot rank compactly)
     u32 *d_sp_g0 = nullptr, *d_sp_n = nullptr, *d_grp_sp = nullptr;
     u32* d_real2pad = nullptr;               // [n_genomes] caller's genome index -> padded index
+    std::vector<u32> col_len;                // [n_genomes] the caller's col_len, lifted hashes included (the order of skx_stream_winners)
     u64* d_mat = nullptr;  // [n_tiles][s][256]
     u64 *d_lo = nullptr, *d_hi = nullptr;  // [n_bands * n_tiles]
     u64 max_ref = 0;       // largest hash in the matrix (queries above it cannot match)
@@ -540,6 +542,7 @@ SKX_API int skx_ref_create_multi(skx_ref** out, int device, uint32_t k, uint64_t
 
     // validate (the reference assumes ascending columns, src/sketchy.rs:416-418; here it is checked)
     std::vector<u32> eff(total);
+    r->col_len.resize(total);
     std::vector<u32> exc_g;
     std::vector<u64> exc_h;
     u64 max_ref = 0;
@@ -556,6 +559,7 @@ SKX_API int skx_ref_create_multi(skx_ref** out, int device, uint32_t k, uint64_t
                 exc_g.push_back(r->sp_g0[sp] + g); exc_h.push_back(col[e - 1]); --e;
             }
             eff[r->sp_real0[sp] + g] = e;
+            r->col_len[r->sp_real0[sp] + g] = len;
             if (e > 0) { any = true; max_ref = std::max<u64>(max_ref, col[e - 1]); }
         }
     }
@@ -1021,7 +1025,9 @@ struct DevMem {  // a device allocation that grows on demand and is freed on eve
 // d_cov_wide the same widened for the ranking; d_dep_pad = the depth walk's results in padded order, one allocation {total [n_pad] u64,
 // covered, max, median [n_pad] u32}; d_dep_vals = the select's scratch (first query; dep_vals_groups groups of 64 genomes per launch);
 // d_dep_n = two counters of export / import; list = what a query of n genomes needs beside that, {total u64, covered, median, requested
-// genomes, their groups u32} [list_cap] (stats_list_room).
+// genomes, their groups u32} [list_cap] (stats_list_room).  Winner-takes-all breadth (first skx_stream_winners* query): d_win = one u32
+// per bit of d_seen (the lowest rank among a seen hash's holders), d_win_rank / d_won [n_pad] = a padded genome's position in the order
+// and what it won.
 struct StreamStats {
     u32* d_seen = nullptr;
     u32 seen_words = 0;
@@ -1030,6 +1036,7 @@ struct StreamStats {
     u32 *d_depth = nullptr, *d_dep_tmp = nullptr, *d_dep_pad = nullptr, *d_dep_vals = nullptr;
     unsigned long long* d_dep_n = nullptr;
     u32 dep_vals_groups = 0, dep_tmp_n = 0;
+    u32 *d_win = nullptr, *d_win_rank = nullptr, *d_won = nullptr;
     DevMem list;
     u32 list_cap = 0;
     u64* l_tot() const { return list.as<u64>(); }
@@ -1040,7 +1047,7 @@ struct StreamStats {
 };
 void stats_free(StreamStats& ss) {  // (the list frees itself)
     for (void* p : {(void*)ss.d_seen, (void*)ss.d_cov_pad, (void*)ss.d_cov_wide, (void*)ss.d_depth, (void*)ss.d_dep_tmp, (void*)ss.d_dep_pad,
-                    (void*)ss.d_dep_vals, (void*)ss.d_dep_n}) (void)hipFree(p);
+                    (void*)ss.d_dep_vals, (void*)ss.d_dep_n, (void*)ss.d_win, (void*)ss.d_win_rank, (void*)ss.d_won}) (void)hipFree(p);
 }
 }  // namespace
 struct skx_stream {
@@ -4396,6 +4403,125 @@ SKX_API int skx_stream_coverage_rank(skx_stream* st, uint32_t top_k, uint32_t* i
     std::vector<uint64_t> sum((size_t)ref->n_species * top_k);
     SKXCHK(rank_padded(st, st->hs, st->stats.d_cov_wide, top_k, idx, sum.data()));
     for (size_t i = 0; i < sum.size(); ++i) covered[i] = (u32)sum[i];
+    return SKX_OK;
+}
+
+// ------------------------------------------------------------------ winner-takes-all breadth
+// won[g] = seen hashes of genome g's column that are credited to g: every seen hash goes to ONE of its holders, the first of them in the
+// global order (containment as an exact fraction, then covered, then the index: skx_winner_order.hpp) -- `mash screen -w`, one round.
+// Nothing is kept between queries and the passes know nothing of it: a query (1) counts the whole table (coverage_walk), (2) brings
+// the counts to the host, sorts, and sends rank[padded genome] back, (3) marks win[hash] = lowest rank among its holders over the whole
+// table and (4) counts, for the groups asked for, the entries whose hash the genome won.  Everything on the scan stream behind the marks
+// of the passes, which is waited for on every way out.
+static hipError_t winners_room(skx_stream* st) {
+    StreamStats& ss = st->stats;
+    if (ss.d_win) return hipSuccess;
+    const skx_ref* ref = st->ref;
+    u32 *win = nullptr, *rank = nullptr, *won = nullptr;
+    hipError_t e = hipMalloc(&win, ((size_t)ref->kt_mask + 3u) * 4);
+    if (e == hipSuccess) e = hipMalloc(&rank, (size_t)ref->n_pad * 4);
+    if (e == hipSuccess) e = hipMalloc(&won, (size_t)ref->n_pad * 4);
+    if (e != hipSuccess) { (void)hipFree(win); (void)hipFree(rank); (void)hipFree(won); return e; }
+    ss.d_win_rank = rank; ss.d_won = won; ss.d_win = win;
+    return hipSuccess;
+}
+static double winners_ms(std::chrono::steady_clock::time_point a) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count();
+}
+// steps (1) to (4); leaves covered in d_cov_pad (the whole table) and won in d_won (the genomes of the groups), queued on st->hs.
+// The caller has flushed and waits for the stream whatever this returns.
+static hipError_t winners_walks(skx_stream* st, const u32* d_groups, u32 n_groups) {
+    const skx_ref* ref = st->ref;
+    StreamStats& ss = st->stats;
+    hipError_t e = winners_room(st);
+    if (e != hipSuccess) return e;
+    const u32 n_pad = ref->n_pad;
+    std::vector<u32> cov(n_pad), order, rank;
+    const bool timed = skx::knob("SKX_WINNERS_TIMES") != nullptr;  // experiment knob: the host's part of a query, to stderr
+    if ((e = coverage_walk(st, nullptr, 0)) != hipSuccess) return e;
+    if (timed && (e = hipStreamSynchronize(st->hs)) != hipSuccess) return e;
+    auto t0 = std::chrono::steady_clock::now();
+    if ((e = hipMemcpyAsync(cov.data(), ss.d_cov_pad, (size_t)n_pad * 4, hipMemcpyDeviceToHost, st->hs)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(st->hs)) != hipSuccess) return e;
+    const double ms_down = winners_ms(t0);
+    t0 = std::chrono::steady_clock::now();
+    skx::winner_ranks(ref->n_species, ref->sp_n.data(), ref->sp_g0.data(), cov.data(), ref->col_len.data(), n_pad, order, rank);
+    const double ms_sort = winners_ms(t0);
+    t0 = std::chrono::steady_clock::now();
+    // (rank is pageable memory: the copy has left it when the call returns)
+    if ((e = hipMemcpyAsync(ss.d_win_rank, rank.data(), (size_t)n_pad * 4, hipMemcpyHostToDevice, st->hs)) != hipSuccess) return e;
+    if ((e = hipStreamSynchronize(st->hs)) != hipSuccess) return e;
+    if (timed) fprintf(stderr, "winners host: copy down %.3f ms, sort %.3f ms, copy up %.3f ms\n", ms_down, ms_sort, winners_ms(t0));
+    if ((e = hipMemsetAsync(ss.d_win, 0xFF, ((size_t)ref->kt_mask + 3u) * 4, st->hs)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(ss.d_won, 0, (size_t)n_pad * 4, st->hs)) != hipSuccess) return e;
+    skx::launch_winner_mark(st->hs, ref->d_mat, ref->s, n_pad / 64u, ref->d_kt_key, ref->kt_mask, ss.d_seen, ref->d_exc_g, ref->d_exc_h, ref->n_exc,
+                            ss.d_win_rank, ss.d_win);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    skx::launch_winner_count(st->hs, ref->d_mat, ref->s, d_groups, d_groups ? n_groups : n_pad / 64u, ref->d_kt_key, ref->kt_mask, ss.d_seen,
+                             ref->d_exc_g, ref->d_exc_h, ref->n_exc, ss.d_win_rank, ss.d_win, ss.d_won);
+    return hipGetLastError();
+}
+// skx_stream_winners (genomes == NULL) and skx_stream_winners_rows: stats_query's shape with the walks above
+static int winners_query(skx_stream* st, const char* fn, const uint32_t* genomes, u32 n, uint32_t* covered, uint32_t* won) {
+    const skx_ref* ref = st->ref;
+    StreamStats& ss = st->stats;
+    std::vector<u32> grp;
+    if (genomes) {
+        const u32 bad = skx::genome_groups(ref->n_species, ref->sp_real0.data(), ref->sp_g0.data(), ref->n_genomes, genomes, n, grp);
+        if (bad < n) return fail(SKX_ERR_INVALID, "%s: genomes[%u] = %u outside 0..n_genomes - 1 = %u", fn, bad, genomes[bad], ref->n_genomes - 1);
+    } else n = ref->n_genomes;
+    SKXCHK(use_device(st->device));
+    SKXCHK(flush_pending(st));
+    SKXCHK(stats_list_room(st, n));
+    hipError_t e = hipSuccess;
+    if (genomes) {
+        e = hipMemcpyAsync(ss.l_gen(), genomes, (size_t)n * 4, hipMemcpyHostToDevice, st->hs);
+        if (e == hipSuccess) e = hipMemcpyAsync(ss.l_grp(), grp.data(), grp.size() * 4, hipMemcpyHostToDevice, st->hs);
+    }
+    if (e == hipSuccess) e = winners_walks(st, genomes ? ss.l_grp() : nullptr, (u32)grp.size());
+    if (e == hipSuccess) {  // (the gather's second u32 column carries won)
+        skx::launch_genome_gather(st->hs, ss.d_cov_pad, ss.d_won, nullptr, ref->d_real2pad, genomes ? ss.l_gen() : nullptr, n,
+                                  covered ? ss.l_cov() : nullptr, won ? ss.l_med() : nullptr, nullptr);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && covered) e = hipMemcpyAsync(covered, ss.l_cov(), (size_t)n * 4, hipMemcpyDeviceToHost, st->hs);
+    if (e == hipSuccess && won) e = hipMemcpyAsync(won, ss.l_med(), (size_t)n * 4, hipMemcpyDeviceToHost, st->hs);
+    const hipError_t e2 = hipStreamSynchronize(st->hs);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(SKX_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+    return SKX_OK;
+}
+SKX_API int skx_stream_winners(skx_stream* st, uint32_t* covered, uint32_t* won) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (!st->stats.d_seen) return fail(SKX_ERR_INVALID, "skx_stream_winners: coverage was never enabled on this stream");
+    return winners_query(st, "skx_stream_winners", nullptr, 0, covered, won);
+}
+SKX_API int skx_stream_winners_rows(skx_stream* st, const uint32_t* genomes, uint32_t n, uint32_t* covered, uint32_t* won) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (!st->stats.d_seen) return fail(SKX_ERR_INVALID, "skx_stream_winners_rows: coverage was never enabled on this stream");
+    if (n == 0) return SKX_OK;
+    if (!genomes) return fail(SKX_ERR_INVALID, "NULL argument");
+    return winners_query(st, "skx_stream_winners_rows", genomes, n, covered, won);
+}
+SKX_API int skx_stream_winners_rank(skx_stream* st, uint32_t top_k, uint32_t* idx, uint32_t* won) {
+    if (!st || !idx || !won) return fail(SKX_ERR_INVALID, "NULL argument");
+    if (!st->stats.d_seen) return fail(SKX_ERR_INVALID, "skx_stream_winners_rank: coverage was never enabled on this stream");
+    const skx_ref* ref = st->ref;
+    if (top_k < 1 || top_k > ref->min_species) return fail(SKX_ERR_INVALID, "skx_stream_winners_rank: top_k=%u outside 1..%u (the smallest species)", top_k, ref->min_species);
+    SKXCHK(use_device(st->device));
+    SKXCHK(flush_pending(st));
+    hipError_t e = winners_walks(st, nullptr, 0);
+    if (e == hipSuccess) {
+        skx::launch_coverage_widen(st->hs, st->stats.d_won, ref->n_pad, st->stats.d_cov_wide);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st->hs);
+        return fail(SKX_ERR_HIP, "skx_stream_winners_rank: %s", hipGetErrorString(e));
+    }
+    std::vector<uint64_t> sum((size_t)ref->n_species * top_k);
+    SKXCHK(rank_padded(st, st->hs, st->stats.d_cov_wide, top_k, idx, sum.data()));
+    for (size_t i = 0; i < sum.size(); ++i) won[i] = (u32)sum[i];
     return SKX_OK;
 }
 SKX_API int skx_stream_depth(skx_stream* st, uint32_t* covered, uint32_t* median, uint64_t* total) {

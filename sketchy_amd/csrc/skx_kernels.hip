@@ -4421,6 +4421,22 @@ template <bool DEPTH> __device__ __forceinline__ u32 stat_value(const u32* __res
     if constexpr (DEPTH) return state[i];
     else return (state[i >> 5] >> (i & 31u)) & 1u;
 }
+// The probe of every walk over the matrix (stat_walk, winner_walk): the lane's column at the ranks r, r + 4, r + 8, r + 12 (below r1) ->
+// sl[j] = key-table slot of the hash there, kSlotNone for padding and ranks beyond r1.  The four loads, then the four start slots, then
+// the four dependent walks: four probes in flight per lane.
+__device__ __forceinline__ void stat_probe4(const u64* __restrict__ col, u32 r, u32 r1, const u64* __restrict__ key, u32 mask, u32 (&sl)[4]) {
+    u64 h[4];
+    u32 slot[4];
+#pragma unroll
+    for (u32 j = 0; j < 4u; ++j) {
+        const u32 rr = r + 4u * j;
+        h[j] = rr < r1 ? col[(size_t)rr * kTileGenomes] : kPad;
+    }
+#pragma unroll
+    for (u32 j = 0; j < 4u; ++j) slot[j] = kt_start(h[j], mask);
+#pragma unroll
+    for (u32 j = 0; j < 4u; ++j) sl[j] = h[j] < kEmpty ? kt_find(key, mask, h[j], slot[j]) : kSlotNone;  // (found always: every stored hash is a key)
+}
 template <bool DEPTH>
 __device__ __forceinline__ void stat_walk(const u64* __restrict__ mat, u32 s, u32 group, const u64* __restrict__ key, u32 mask,
                                           const u32* __restrict__ state, const u32* __restrict__ exc_g, const u64* __restrict__ exc_h,
@@ -4435,22 +4451,11 @@ __device__ __forceinline__ void stat_walk(const u64* __restrict__ mat, u32 s, u3
     u32 n = 0, mx = 0;
     u64 tot = 0;
     for (u32 r = r0 + wv; r < r1; r += 16u) {
-        u64 h[4];
-        u32 slot[4];
+        u32 sl[4];
+        stat_probe4(col, r, r1, key, mask, sl);
 #pragma unroll
         for (u32 j = 0; j < 4u; ++j) {
-            const u32 rr = r + 4u * j;
-            h[j] = rr < r1 ? col[(size_t)rr * kTileGenomes] : kPad;
-        }
-#pragma unroll
-        for (u32 j = 0; j < 4u; ++j) slot[j] = kt_start(h[j], mask);
-#pragma unroll
-        for (u32 j = 0; j < 4u; ++j) {
-            u32 v = 0;  // (padding, a rank beyond r1: nothing)
-            if (h[j] < kEmpty) {
-                const u32 sl = kt_find(key, mask, h[j], slot[j]);
-                if (sl != kSlotNone) v = stat_value<DEPTH>(state, sl);  // (always: every stored hash is a key)
-            }
+            const u32 v = sl[j] != kSlotNone ? stat_value<DEPTH>(state, sl[j]) : 0u;  // (padding, a rank beyond r1: nothing)
             if constexpr (DEPTH) {
                 const u32 rr = r + 4u * j;
                 if (rr < r1) out[(size_t)rr * 64u + lane] = v;
@@ -4506,6 +4511,91 @@ __global__ void genome_gather_kernel(const u32* __restrict__ covered, const u32*
 __global__ void coverage_widen_kernel(const u32* __restrict__ covered, u32 n_pad, u64* __restrict__ wide) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n_pad) wide[i] = covered[i];
+}
+
+// Winner-takes-all breadth (skx_stream_winners): every seen hash is credited to ONE of its holders, the first of them in the global order
+// the host built from the plain counts (skx_winner_order.hpp; rank[p] = position of padded genome p in it, 0xFFFFFFFF for padding
+// genomes).  Two walks over stat_walk's traversal -- lane = genome of an aligned 64-genome group, stat_probe4, the lifted hashes in the
+// block of rank chunk 0 -- and one u32 per index of the seen set:
+//   winner_mark_kernel   the whole table, always (every holder of a hash can be its winner): win[index] = min over the holders' ranks,
+//                        0xFFFFFFFF on entry.  The lanes of a wave mostly meet on one index (clones hold a hash at the same rank), so the
+//                        wave sends one atomicMin per DISTINCT index, carrying the lowest rank among its lanes there (depth_count_kernel's
+//                        ballot loop); a lane whose plain load of win[index] is below its rank already has nothing to send.  That load may
+//                        be stale: the values only fall, so a stale one only costs an atomic -- the atomicMin decides.
+//   winner_count_kernel  the groups asked for, in a launch of its own behind the mark walk (the kernel boundary is the ordering):
+//                        won[p] += seen entries of p's column with win[index] == rank[p]; partial sums through LDS, one atomicAdd per
+//                        genome and block (won zero on entry for the walked genomes).
+// An entry that is not seen contributes nothing to either.
+__device__ __forceinline__ bool seen_bit(const u32* __restrict__ seen, u32 i) { return (seen[i >> 5] >> (i & 31u)) & 1u; }
+// wave-uniform: every lane with at != kSlotNone offers rk for win[at]
+__device__ __forceinline__ void winner_offer(u32* win, u32 at, u32 rk) {
+    if (at != kSlotNone && win[at] < rk) at = kSlotNone;
+    u64 todo = __ballot(at != kSlotNone);
+    const u64 me = 1ull << (threadIdx.x & 63u);
+    while (todo) {
+        const u32 first = __shfl(at, __ffsll((long long)todo) - 1);
+        const u64 same = __ballot(at == first) & todo;
+        u32 low = at == first ? rk : 0xFFFFFFFFu;
+        if (same & (same - 1ull)) {  // (more than one lane: the lowest rank among them)
+#pragma unroll
+            for (u32 d = 32u; d; d >>= 1) low = min(low, (u32)__shfl_xor((int)low, (int)d));
+        }
+        if ((same & (0ull - same)) == me) atomicMin(&win[first], low);
+        todo &= ~same;
+    }
+}
+template <bool COUNT>
+__device__ __forceinline__ void winner_walk(const u64* __restrict__ mat, u32 s, u32 group, const u64* __restrict__ key, u32 mask,
+                                            const u32* __restrict__ seen, const u32* __restrict__ exc_g, const u64* __restrict__ exc_h,
+                                            u32 n_exc, const u32* __restrict__ rank, u32* win, u32* __restrict__ won) {
+    __shared__ u32 part_n[4][64];
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u32 p = group * 64u + lane;
+    const u64* col = mat + (size_t)(p / kTileGenomes) * s * kTileGenomes + p % kTileGenomes;
+    const u32 r0 = blockIdx.y * kCovRanks, r1 = min(s, r0 + kCovRanks);
+    const u32 rk = rank[p];
+    u32 n = 0;
+    for (u32 r = r0 + wv; r < r1; r += 16u) {  // (r, r1 are the wave's: the ballots below see all 64 lanes)
+        u32 sl[4];
+        stat_probe4(col, r, r1, key, mask, sl);
+#pragma unroll
+        for (u32 j = 0; j < 4u; ++j) {
+            const u32 at = sl[j] != kSlotNone && seen_bit(seen, sl[j]) ? sl[j] : kSlotNone;
+            if constexpr (COUNT) n += at != kSlotNone && win[at] == rk;
+            else winner_offer(win, at, rk);
+        }
+    }
+    if (blockIdx.y == 0 && wv == 0) {
+        u32 lv[2] = {kSlotNone, kSlotNone};  // the indices of the genome's lifted hashes kEmpty and kEmpty + 1, where they are seen
+        for (u32 a = exc_first(exc_g, n_exc, p); a < n_exc && exc_g[a] == p; ++a) {
+            const u32 w = (u32)(exc_h[a] - kEmpty) & 1u;
+            if (seen_bit(seen, mask + 1u + w)) lv[w] = mask + 1u + w;
+        }
+#pragma unroll
+        for (u32 w = 0; w < 2u; ++w) {
+            if constexpr (COUNT) n += lv[w] != kSlotNone && win[lv[w]] == rk;
+            else winner_offer(win, lv[w], rk);
+        }
+    }
+    if constexpr (COUNT) {
+        part_n[wv][lane] = n;
+        __syncthreads();
+        if (wv == 0) {
+            const u32 tn = part_n[0][lane] + part_n[1][lane] + part_n[2][lane] + part_n[3][lane];
+            if (tn) atomicAdd(&won[p], tn);
+        }
+    }
+}
+__global__ __launch_bounds__(256) void winner_mark_kernel(const u64* __restrict__ mat, u32 s, const u64* __restrict__ key, u32 mask,
+                                                          const u32* __restrict__ seen, const u32* __restrict__ exc_g,
+                                                          const u64* __restrict__ exc_h, u32 n_exc, const u32* __restrict__ rank, u32* win) {
+    winner_walk<false>(mat, s, blockIdx.x, key, mask, seen, exc_g, exc_h, n_exc, rank, win, nullptr);
+}
+__global__ __launch_bounds__(256) void winner_count_kernel(const u64* __restrict__ mat, u32 s, const u32* __restrict__ groups,
+                                                           const u64* __restrict__ key, u32 mask, const u32* __restrict__ seen,
+                                                           const u32* __restrict__ exc_g, const u64* __restrict__ exc_h, u32 n_exc,
+                                                           const u32* __restrict__ rank, const u32* win, u32* __restrict__ won) {
+    winner_walk<true>(mat, s, groups ? groups[blockIdx.x] : blockIdx.x, key, mask, seen, exc_g, exc_h, n_exc, rank, const_cast<u32*>(win), won);
 }
 
 // =====================================================================================
@@ -6552,6 +6642,18 @@ void launch_genome_gather(hipStream_t st, const u32* covered, const u32* median,
     if (n == 0) return;
     hipLaunchKernelGGL(genome_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, st, covered, median, total, real2pad, genomes, n, out_cov,
                        out_med, out_tot);
+}
+void launch_winner_mark(hipStream_t st, const u64* mat, u32 s, u32 n_groups, const u64* key, u32 mask, const u32* seen, const u32* exc_g,
+                        const u64* exc_h, u32 n_exc, const u32* rank, u32* win) {
+    if (n_groups == 0 || s == 0) return;
+    hipLaunchKernelGGL(winner_mark_kernel, dim3(n_groups, cdiv(s, kCovRanks)), dim3(256), 0, st, mat, s, key, mask, seen, exc_g, exc_h, n_exc, rank,
+                       win);
+}
+void launch_winner_count(hipStream_t st, const u64* mat, u32 s, const u32* groups, u32 n_groups, const u64* key, u32 mask, const u32* seen,
+                         const u32* exc_g, const u64* exc_h, u32 n_exc, const u32* rank, const u32* win, u32* won) {
+    if (n_groups == 0 || s == 0) return;
+    hipLaunchKernelGGL(winner_count_kernel, dim3(n_groups, cdiv(s, kCovRanks)), dim3(256), 0, st, mat, s, groups, key, mask, seen, exc_g, exc_h,
+                       n_exc, rank, win, won);
 }
 void launch_coverage_widen(hipStream_t st, const u32* covered, u32 n_pad, u64* wide) {
     hipLaunchKernelGGL(coverage_widen_kernel, dim3(cdiv(n_pad, 256)), dim3(256), 0, st, covered, n_pad, wide);

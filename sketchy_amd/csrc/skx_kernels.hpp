@@ -414,6 +414,15 @@ void launch_coverage_walk(hipStream_t st, const u64* mat, u32 s, const u32* grou
 void launch_genome_gather(hipStream_t st, const u32* covered, const u32* median, const u64* total, const u32* real2pad, const u32* genomes,
                           u32 n, u32* out_cov, u32* out_med, u64* out_tot);
 void launch_coverage_widen(hipStream_t st, const u32* covered, u32 n_pad, u64* wide);
+// ---- winner-takes-all breadth (skx_kernels.hip, "Winner-takes-all breadth").  rank [n_pad]: a padded genome's position in the global
+// order (skx_winner_order.hpp), 0xFFFFFFFF for padding genomes; win: one u32 per bit of `seen`, same indices.
+// launch_winner_mark: the whole table (groups 0 .. n_groups - 1); win all-ones on entry, afterwards the lowest rank among the holders of
+// every seen hash.  launch_winner_count, behind it on the same stream: won[p] += seen hashes of padded genome p with win == rank[p], for
+// the genomes of groups[0 .. n_groups) (NULL: the whole table); won [n_pad], zero on entry for those genomes
+void launch_winner_mark(hipStream_t st, const u64* mat, u32 s, u32 n_groups, const u64* key, u32 mask, const u32* seen, const u32* exc_g,
+                        const u64* exc_h, u32 n_exc, const u32* rank, u32* win);
+void launch_winner_count(hipStream_t st, const u64* mat, u32 s, const u32* groups, u32 n_groups, const u64* key, u32 mask, const u32* seen,
+                         const u32* exc_g, const u64* exc_h, u32 n_exc, const u32* rank, const u32* win, u32* won);
 // ---- depth of a stream (skx_kernels.hip, "depth of a stream").  depth: one u32 per bit of `seen`, same indices, saturating.
 // launch_depth_mark: behind launch_pair_q of the same pass, same stream (pair_h, q, n_q, bbase, btot: its; qinfo: its launch_classify's);
 // tmp [>= q_bound] is zero on entry and zero again afterwards.

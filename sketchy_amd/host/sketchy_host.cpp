@@ -86,6 +86,8 @@ extern "C" int skx_stream_table(skx_stream* st, uint64_t* cum) __attribute__((we
 extern "C" int skx_stream_enable_depth(skx_stream* st) __attribute__((weak));
 extern "C" int skx_stream_depth_rows(skx_stream* st, const uint32_t* genomes, uint32_t n, uint32_t* covered, uint32_t* median, uint64_t* total)
     __attribute__((weak));
+// ... and the breadth with every seen hash credited to one sketch (`screen --winner-take-all`): the winner is a property of each hash
+extern "C" int skx_stream_winners(skx_stream* st, uint32_t* covered, uint32_t* won) __attribute__((weak));
 
 namespace sketchy {
 
@@ -331,8 +333,12 @@ class Sketchy {
     // (ties: the sketch earlier in the file) are printed.  One reference only: several -r are not built.
     // depth: also the median multiplicity of the printed sketches (the lower median of how many reads shared each covered hash), from
     // skx_stream_depth_rows of the TOP rows; identity: Mash screen's containment^(1/k), computed here.
+    // winners (`mash screen -w`): every seen hash is credited to ONE sketch, the best of its holders (skx_stream_winners); the rows are
+    // then ordered by won / size (ties: the larger plain containment, then the sketch earlier in the file), two columns -- won and
+    // winner_containment -- follow shared_hashes, and the identity is taken from the winner containment, as Mash does.
     void screen(const std::string& fastx, const std::string& reference, const std::string& genotypes, size_t top, size_t limit, bool header,
-                std::ostream& out, bool depth = false, bool identity = false) {
+                std::ostream& out, bool depth = false, bool identity = false, bool winners = false) {
+        if (winners && !skx_stream_winners) throw UsageError("screen --winner-take-all needs skx_stream_winners, which the loaded libsketchy_hip does not export");
         if (depth && !skx_stream_enable_depth) throw UsageError("screen --depth needs skx_stream_enable_depth, which the loaded libsketchy_hip does not export");
         if (depth && !skx_stream_depth_rows) throw UsageError("screen --depth needs skx_stream_depth_rows, which the loaded libsketchy_hip does not export");
         // there is no host route to the number: a library without the entry points ends here, before anything is read
@@ -354,7 +360,7 @@ class Sketchy {
         const uint64_t max_bases = 1ull << 28;
         skx_stream* st = nullptr;
         hip_check(skx_stream_create(&st, ref.h, 0, (uint32_t)batch_, max_bases), "stream");
-        std::vector<uint32_t> covered(n), order(n), median(depth ? top : 0);
+        std::vector<uint32_t> covered(n), order(n), median(depth ? top : 0), won(winners ? n : 0);
         std::vector<uint64_t> sum(n);
         for (size_t g = 0; g < n; ++g) order[g] = (uint32_t)g;
         auto size_of = [&](uint32_t g) { return (uint64_t)sketches[g].hashes.size(); };
@@ -376,11 +382,16 @@ class Sketchy {
                 if (reads == limit) break;
             }
             flush();
-            hip_check(skx_stream_coverage(st, covered.data()), "screen");
+            if (winners) hip_check(skx_stream_winners(st, covered.data(), won.data()), "screen");
+            else hip_check(skx_stream_coverage(st, covered.data()), "screen");
             hip_check(skx_stream_table(st, sum.data()), "screen");
             // by containment = covered / size, compared as fractions (exact); an empty sketch contains nothing
+            auto more_of = [&](const std::vector<uint32_t>& v, uint32_t x, uint32_t y) {
+                return (uint64_t)v[x] * std::max<uint64_t>(size_of(y), 1) > (uint64_t)v[y] * std::max<uint64_t>(size_of(x), 1);
+            };
             std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-                return (uint64_t)covered[x] * std::max<uint64_t>(size_of(y), 1) > (uint64_t)covered[y] * std::max<uint64_t>(size_of(x), 1);
+                if (winners && (more_of(won, x, y) || more_of(won, y, x))) return more_of(won, x, y);
+                return more_of(covered, x, y);
             });
             if (depth) hip_check(skx_stream_depth_rows(st, order.data(), (uint32_t)top, nullptr, median.data(), nullptr), "screen");
         } catch (...) {
@@ -389,7 +400,8 @@ class Sketchy {
         }
         skx_stream_destroy(st);
         if (header)
-            out << "sketch_id\tcovered\tsketch_size\tcontainment\tshared_hashes" << (depth ? "\tmedian_multiplicity" : "") << (identity ? "\tidentity" : "")
+            out << "sketch_id\tcovered\tsketch_size\tcontainment\tshared_hashes" << (winners ? "\twon\twinner_containment" : "")
+                << (depth ? "\tmedian_multiplicity" : "") << (identity ? "\tidentity" : "")
                 << (with_geno ? "\t" + geno.header : std::string()) << "\n";
         char buf[32];
         for (size_t j = 0; j < top; ++j) {
@@ -397,9 +409,14 @@ class Sketchy {
             const double containment = size_of(g) ? (double)covered[g] / (double)size_of(g) : 0.0;
             std::snprintf(buf, sizeof buf, "%.6f", containment);
             out << sketches[g].name << "\t" << covered[g] << "\t" << size_of(g) << "\t" << buf << "\t" << sum[g];
+            const double won_containment = winners && size_of(g) ? (double)won[g] / (double)size_of(g) : 0.0;
+            if (winners) {
+                std::snprintf(buf, sizeof buf, "%.6f", won_containment);
+                out << "\t" << won[g] << "\t" << buf;
+            }
             if (depth) out << "\t" << median[j];
             if (identity) {
-                std::snprintf(buf, sizeof buf, "%.6f", std::pow(containment, 1.0 / (double)std::max<uint32_t>(sketches[g].kmer_length, 1u)));
+                std::snprintf(buf, sizeof buf, "%.6f", std::pow(winners ? won_containment : containment, 1.0 / (double)std::max<uint32_t>(sketches[g].kmer_length, 1u)));
                 out << "\t" << buf;
             }
             if (with_geno) out << "\t" << join_tab(geno.map.at(sketches[g].name));
@@ -1461,12 +1478,15 @@ static void usage() {
                  "                    sketch_id neighbour_id shared_hashes [the neighbour's genotype columns]; -c, with -g and an odd TOP: one line per\n"
                  "                    sketch, the consensus of its neighbours; -S / --summary, with -g: one line per genotype column -- column, the\n"
                  "                    sketches whose own value is that consensus, all sketches)\n"
-                 "sketchy-hip screen  -r REF.msh -i READS.fx[.gz] [-g GENO.tsv] [-t TOP=10] [-l LIMIT] [-H] [-d] [-I]\n"
+                 "sketchy-hip screen  -r REF.msh -i READS.fx[.gz] [-g GENO.tsv] [-t TOP=10] [-l LIMIT] [-H] [-d] [-I] [-w]\n"
                  "                    (containment of every sketch of REF in the read set: the TOP sketches by covered / sketch_size --\n"
                  "                    sketch_id covered sketch_size containment shared_hashes [median_multiplicity] [identity] [genotype columns];\n"
                  "                    covered = hashes of the sketch that at least one read shared; -d / --depth: median_multiplicity = the lower\n"
                  "                    median of the number of reads that shared each covered hash; -I / --identity: containment^(1/k); here -d\n"
-                 "                    is --depth, the device is chosen with --device; one reference: several -r are not built)\n"
+                 "                    is --depth, the device is chosen with --device; one reference: several -r are not built;\n"
+                 "                    -w / --winner-take-all: every seen hash is credited to ONE sketch, the best of those that hold it (by\n"
+                 "                    containment, then covered, then file order): the TOP sketches by won / sketch_size, the columns won and\n"
+                 "                    winner_containment behind shared_hashes, the identity from the winner containment)\n"
                  "sketchy-hip shared  -r REF.msh -q QUERY.msh\n"
                  "sketchy-hip info    -i SKETCH.msh [-p]\n"
                  "sketchy-hip check   -r REF.msh -g GENO.tsv\n");
@@ -1489,6 +1509,7 @@ int main(int argc, char** argv) {
         if (is_sketch && a == "--stream") { usage(); return 2; }
         if (cmd == "screen" && (a == "-d" || a == "--depth")) { flag["--depth"] = true; continue; }  // (`screen`: -d is --depth; the device: --device)
         if (cmd == "screen" && (a == "-I" || a == "--identity")) { flag["--identity"] = true; continue; }
+        if (cmd == "screen" && (a == "-w" || a == "--winner-take-all")) { flag["--winner-take-all"] = true; continue; }
         if (longnames.count(a)) a = longnames.at(a);
         // (predict: a lone "-" is a path -- stdin)
         if (many_inputs && a == "-i") { while (i + 1 < argc && (argv[i + 1][0] != '-' || (!is_sketch && !argv[i + 1][1]))) inputs.push_back(argv[++i]); continue; }
@@ -1560,7 +1581,7 @@ int main(int argc, char** argv) {
             const long top = opt.count("-t") ? std::atol(opt["-t"].c_str()) : 10, limit = opt.count("-l") ? std::atol(opt["-l"].c_str()) : 0;
             if (top < 1) { std::fprintf(stderr, "Error: --top must be at least 1\n"); return 2; }
             app.screen(opt["-i"], opt["-r"], opt.count("-g") ? opt["-g"] : std::string(), (size_t)top, (size_t)std::max(0L, limit), flag["-H"], std::cout,
-                       flag["--depth"], flag["--identity"]);
+                       flag["--depth"], flag["--identity"], flag["--winner-take-all"]);
         } else if (cmd == "shared") {
             if (!opt.count("-r") || !opt.count("-q")) { usage(); return 2; }
             app.shared(opt["-r"], opt["-q"], std::cout);

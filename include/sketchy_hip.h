@@ -33,6 +33,8 @@
  *                             holders (`mash screen -w`): a clone tree's thousands of copies of one lineage stop outranking a second strain
  *   skx_stream_enable_depth / skx_stream_depth[_rows|_count|_export|_import] <- no counterpart: how OFTEN each of a genome's hashes was
  *                             shared (the median multiplicity of `mash screen`), and the counters as portable (hash, count) pairs
+ *   skx_stream_enable_composition / skx_stream_composition <- no counterpart: reads per resident species, ambiguous and unclassified,
+ *                             each read classified by its own sketch's hits per species
  *   skx_sketch_reads       <- finch SketchScheme::{process,to_vec} as called at :331-335
  *   skx_sketch_groups      <- finch SketchScheme::{process x many, to_vec}: ONE sketcher fed several records -- all reads of an
  *                             offline `predict` (src/sketchy.rs:291-302), all contigs of a genome file in `sketch` (:473-478)
@@ -517,6 +519,36 @@ int skx_stream_depth_rows(skx_stream *st, const uint32_t *genomes, uint32_t n, u
 int skx_stream_depth_count(skx_stream *st, uint64_t *n);
 int skx_stream_depth_export(skx_stream *st, uint64_t *hashes, uint32_t *counts, uint64_t cap, uint64_t *n);
 int skx_stream_depth_import(skx_stream *st, const uint64_t *hashes, const uint32_t *counts, uint64_t n, uint64_t *n_unknown);
+/*
+ * Composition of a stream (no counterpart in the reference binary).  Every other number a stream returns describes the sample as a whole;
+ * the species call names ONE species for the sample.  This says what the sample is made of: how many reads came from each resident
+ * species, counted read by read from the read's OWN sketch -- a 3 % contaminant stays 3 %.
+ * For every read r pushed after skx_stream_enable_composition(st, min_hits), with K_r its bottom-s sketch (truncation first, as everywhere):
+ *   hits[r][sp] = |{h in K_r : some genome of species sp holds h inside its col_len}|
+ * A hash held by two species counts for both.  The lifted values 0xFF..FE and 0xFF..FF count for nobody: no read hashes to them.
+ * With best = max over sp of hits[r][sp] the read falls into exactly one class:
+ *   best < min_hits                  unclassified (reads without a valid k-mer and reads whose hashes nobody holds are here)
+ *   one species attains best         that species
+ *   several species attain best      ambiguous -- there is NO lowest-index tie rule: a tie is not credited to anybody
+ * The stream keeps, as uint64_t:
+ *   reads[n_species + 2]  reads per species, then ambiguous, then unclassified; their sum is the reads pushed since enable or reset,
+ *                         whichever entry point brought them and however a batch was cut into passes or shared one
+ *   pairs[n_species]      pairs[sp] += hits[r][sp] for every read, whatever its class
+ * With one species reads[0] is the number of reads that hit the reference at least min_hits times (the on-target reads).
+ * skx_stream_enable_composition has the preconditions and errors of skx_stream_enable_depth (before the first read or after a reset:
+ * SKX_ERR_INVALID otherwise; no rare-hash index: SKX_ERR_UNSUPPORTED, stream untouched); min_hits == 0: SKX_ERR_INVALID; a second call
+ * with the same min_hits: SKX_OK, with another: SKX_ERR_INVALID; more than 64 species: SKX_ERR_UNSUPPORTED.  It needs neither coverage nor
+ * depth and changes neither.  The first stream that enables it on a reference of several species builds that reference's species masks
+ * (one uint64_t per distinct reference hash, one walk over the resident matrix); they are kept with the skx_ref and freed with it.  Every
+ * scoring pass then classifies its reads on the device.  Rows, table, coverage and depth are what they were.  skx_stream_reset zeroes the
+ * counters and keeps composition enabled; skx_stream_table_add, skx_stream_allreduce and skx_stream_depth_import do not touch them (the
+ * counters are additive: ranks add theirs on the host); skx_stream_destroy frees them.  A stream that never enables composition allocates
+ * and launches nothing.
+ * skx_stream_composition flushes as the coverage queries do and copies the counters; either output may be NULL.
+ * SKX_ERR_INVALID: a NULL stream; a stream that never enabled composition.
+ */
+int skx_stream_enable_composition(skx_stream *st, uint32_t min_hits);
+int skx_stream_composition(skx_stream *st, uint64_t *reads /* [n_species + 2] or NULL */, uint64_t *pairs /* [n_species] or NULL */);
 void skx_stream_destroy(skx_stream *st);
 
 /*

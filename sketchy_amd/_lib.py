@@ -81,6 +81,8 @@ SYMBOLS = [
     ("skx_stream_depth_count", _i, [_vp, C.POINTER(_u64)]),
     ("skx_stream_depth_export", _i, [_vp, _vp, _vp, _u64, C.POINTER(_u64)]),
     ("skx_stream_depth_import", _i, [_vp, _vp, _vp, _u64, C.POINTER(_u64)]),
+    ("skx_stream_enable_composition", _i, [_vp, _u32]),
+    ("skx_stream_composition", _i, [_vp, _vp, _vp]),
     ("skx_stream_destroy", None, [_vp]),
     ("skx_stream_set_profiling", _i, [_vp, _i]),
     ("skx_stream_profile", _i, [_vp, C.POINTER(C.c_double), C.POINTER(_u64)]),

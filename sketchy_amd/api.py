@@ -555,6 +555,19 @@ class SumOfSharedHashes:
         _lib.check(_lib.load().skx_stream_depth_import(self._h, _p(hashes), _p(counts), len(hashes), C.byref(unknown)))
         return int(unknown.value)
 
+    def enable_composition(self, min_hits=1):
+        """Classify every read by its own sketch's hits per species (skx_stream_enable_composition): before the first read, or after
+        reset().  A read whose best species has fewer than `min_hits` hits is unclassified."""
+        _lib.check(_lib.load().skx_stream_enable_composition(self._h, int(min_hits)))
+
+    def composition(self):
+        """(reads, pairs), uint64: reads [n_species + 2] = reads per species, then ambiguous (several species tie for the most hits), then
+        unclassified; pairs [n_species] = the reads' hits per species, whatever their class."""
+        n = self.ref.n_species
+        reads, pairs = np.zeros(n + 2, np.uint64), np.zeros(n, np.uint64)
+        _lib.check(_lib.load().skx_stream_composition(self._h, _p(reads), _p(pairs)))
+        return reads, pairs
+
     def consensus(self, top=None) -> np.ndarray:
         """Consensus codes of the CURRENT table: rank(top) followed by the reference's consensus_rows -> [F] / [n_species, F]."""
         idx, _ = self.rank(top)

@@ -308,6 +308,10 @@ struct skx_ref {
     // species-local index names a genome's row (the padding rows are zero and never asked for)
     u32* d_codes = nullptr;
     u32 n_features = 0;
+    // species mask per key-table slot (bit sp: a genome of species sp holds the key), built by the first stream that enables composition
+    // (ref_species_mask; a reference of one species needs none) and kept for every later one
+    mutable u64* d_spmask = nullptr;
+    mutable std::mutex spmask_mu;
     skx::RareIndex rare_index() const {
         skx::RareIndex ri{d_kt_key, d_kt_off, d_kt_cnt, d_post, kt_mask, d_mlong, d_lid, d_lslot, n_pad / 64, d_mlongT, n_lw};
         ri.prec = d_prec; ri.pat_rep = d_pat_rep; ri.pm = d_pm; ri.d_npat = d_npat; ri.n_pat = n_pat;
@@ -329,6 +333,7 @@ static void ref_free(skx_ref* r) {
     (void)hipFree(r->d_prec); (void)hipFree(r->d_pat_rep); (void)hipFree(r->d_npat); (void)hipFree(r->d_pm);
     (void)hipFree(r->d_qs); (void)hipFree(r->d_nsd); (void)hipFree(r->d_win_s);
     (void)hipFree(r->d_srow); (void)hipFree(r->d_seg); (void)hipFree(r->d_segw); (void)hipFree(r->d_codes);
+    (void)hipFree(r->d_spmask);
     delete r;
 }
 
@@ -1027,7 +1032,8 @@ struct DevMem {  // a device allocation that grows on demand and is freed on eve
 // d_dep_n = two counters of export / import; list = what a query of n genomes needs beside that, {total u64, covered, median, requested
 // genomes, their groups u32} [list_cap] (stats_list_room).  Winner-takes-all breadth (first skx_stream_winners* query): d_win = one u32
 // per bit of d_seen (the lowest rank among a seen hash's holders), d_win_rank / d_won [n_pad] = a padded genome's position in the order
-// and what it won.
+// and what it won.  Composition (skx_stream_enable_composition): d_comp = the counters {reads [n_species + 2], pairs [n_species]} u64,
+// d_comp_qmask [dep_tmp_n's size] = the species mask of a pass's distinct hashes by position in Q; comp_min_hits = 0: never enabled.
 struct StreamStats {
     u32* d_seen = nullptr;
     u32 seen_words = 0;
@@ -1037,6 +1043,8 @@ struct StreamStats {
     unsigned long long* d_dep_n = nullptr;
     u32 dep_vals_groups = 0, dep_tmp_n = 0;
     u32 *d_win = nullptr, *d_win_rank = nullptr, *d_won = nullptr;
+    u64 *d_comp = nullptr, *d_comp_qmask = nullptr;
+    u32 comp_min_hits = 0;
     DevMem list;
     u32 list_cap = 0;
     u64* l_tot() const { return list.as<u64>(); }
@@ -1047,7 +1055,8 @@ struct StreamStats {
 };
 void stats_free(StreamStats& ss) {  // (the list frees itself)
     for (void* p : {(void*)ss.d_seen, (void*)ss.d_cov_pad, (void*)ss.d_cov_wide, (void*)ss.d_depth, (void*)ss.d_dep_tmp, (void*)ss.d_dep_pad,
-                    (void*)ss.d_dep_vals, (void*)ss.d_dep_n, (void*)ss.d_win, (void*)ss.d_win_rank, (void*)ss.d_won}) (void)hipFree(p);
+                    (void*)ss.d_dep_vals, (void*)ss.d_dep_n, (void*)ss.d_win, (void*)ss.d_win_rank, (void*)ss.d_won, (void*)ss.d_comp,
+                    (void*)ss.d_comp_qmask}) (void)hipFree(p);
 }
 }  // namespace
 struct skx_stream {
@@ -2295,6 +2304,20 @@ static int run_pass_multi(skx_stream* st, SubPass* subs, int n_sub, bool update_
             if (st->stats.d_depth && split_dict)
                 skx::launch_depth_mark(hs, st->d_pair_h[b], P, d_q, d_nq, q_bound, st->d_qinfo, st->d_bbase, st->d_btot, ref->max_ref, st->stats.d_dep_tmp,
                                        st->stats.d_depth, ref->kt_mask + 1u);
+            // (a stream with composition enabled: the species masks of the pass's distinct hashes, then every batch's reads by class)
+            if (st->stats.d_comp && update_table && split_dict)
+                skx::launch_comp_qmask(hs, d_q, d_nq, q_bound, st->d_qinfo, ref->d_spmask, ref->kt_mask + 1u, st->stats.d_comp_qmask);
+            HIPCHK(hipGetLastError());
+        }
+        if (st->stats.d_comp && update_table && split_dict) {
+            u64 *c_reads = st->stats.d_comp, *c_pairs = c_reads + ref->n_species + 2u;
+            for (int i = 0; i < n_sub; ++i) {
+                const SubPass& sb = subs[i];
+                if (sb.P == 0) skx::launch_comp_add(hs, c_reads + ref->n_species + 1u, sb.rb - sb.ra);  // (no pair: unclassified, all of them)
+                else
+                    skx::launch_comp_count(hs, st->d_pair_h[b] + sb.p_off, sb.d_poff, sb.p_base, sb.rb - sb.ra, d_q, d_nq, q_bound, st->d_bbase,
+                                           st->d_btot, ref->max_ref, st->stats.d_comp_qmask, ref->n_species, st->stats.comp_min_hits, c_reads, c_pairs);
+            }
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventRecord(st->ev_pairq[b], hs));  // the set's hash set and pair hashes may be refilled
@@ -4124,12 +4147,13 @@ SKX_API int skx_stream_table_add(skx_stream* st, const uint64_t* add) {
     return SKX_OK;
 }
 // a new sample has seen nothing and counted nothing; what was enabled stays enabled
-static int stats_reset(StreamStats& ss, u32 kt_mask, hipStream_t on) {
+static int stats_reset(StreamStats& ss, u32 kt_mask, u32 n_species, hipStream_t on) {
     if (ss.d_seen) HIPCHK(hipMemsetAsync(ss.d_seen, 0, (size_t)ss.seen_words * 4, on));
     if (ss.d_depth) {
         HIPCHK(hipMemsetAsync(ss.d_depth, 0, ((size_t)kt_mask + 3u) * 4, on));
         HIPCHK(hipMemsetAsync(ss.d_dep_tmp, 0, (size_t)ss.dep_tmp_n * 4, on));
     }
+    if (ss.d_comp) HIPCHK(hipMemsetAsync(ss.d_comp, 0, ((size_t)2 * n_species + 2u) * 8, on));
     return SKX_OK;
 }
 SKX_API int skx_stream_reset(skx_stream* st) {
@@ -4140,7 +4164,7 @@ SKX_API int skx_stream_reset(skx_stream* st) {
     HIPCHK(hipStreamSynchronize(st->hs1));
     HIPCHK(hipStreamSynchronize(st->hs));
     HIPCHK(hipMemsetAsync(st->d_cum, 0, (size_t)st->ref->n_pad * 8, st->hs2));
-    SKXCHK(stats_reset(st->stats, st->ref->kt_mask, st->hs2));
+    SKXCHK(stats_reset(st->stats, st->ref->kt_mask, st->ref->n_species, st->hs2));
     HIPCHK(hipStreamSynchronize(st->hs2));
     st->reads_total = 0;
     st->h_nq[2] = 1; st->h_nq[3] = 1;  // (a new sample: every genome is a candidate again)
@@ -4317,6 +4341,74 @@ static hipError_t depth_walk(skx_stream* st, const u32* d_groups, u32 n_groups) 
                                ref->d_exc_g, ref->d_exc_h, ref->n_exc, d_cov, d_tot, d_max, d_med, ss.d_dep_vals);
     }
     return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ composition of a stream
+// Every read pushed falls into one class -- a species, ambiguous, unclassified -- by its own sketch's hits per species (sketchy_hip.h).
+// The counts of every pass run on the scan stream (run_pass_multi, behind the pass's pair_q); the query copies them from there.
+// The reference's side: the species mask of every key-table slot, built once per reference by the first stream that needs it.
+static int ref_species_mask(const skx_ref* ref, hipStream_t on) {
+    std::lock_guard<std::mutex> lk(ref->spmask_mu);
+    if (ref->d_spmask || ref->n_species == 1) return SKX_OK;
+    const size_t bytes = ((size_t)ref->kt_mask + 1u) * 8;
+    u64* m = nullptr;
+    hipError_t e = hipMalloc(&m, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(m, 0, bytes, on);
+    if (e == hipSuccess) {
+        skx::launch_species_mask(on, ref->d_mat, ref->s, ref->n_pad / 64u, ref->d_kt_key, ref->kt_mask, ref->species(), m);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(on);
+    if (e != hipSuccess) {
+        (void)hipFree(m);
+        (void)hipGetLastError();
+        return fail(SKX_ERR_HIP, "skx_stream_enable_composition: the species masks: %s", hipGetErrorString(e));
+    }
+    ref->d_spmask = m;
+    return SKX_OK;
+}
+SKX_API int skx_stream_enable_composition(skx_stream* st, uint32_t min_hits) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (min_hits == 0) return fail(SKX_ERR_INVALID, "skx_stream_enable_composition: min_hits = 0 (at least one hit makes a read a species')");
+    StreamStats& ss = st->stats;
+    if (ss.d_comp) {
+        if (ss.comp_min_hits == min_hits) return SKX_OK;
+        return fail(SKX_ERR_INVALID, "skx_stream_enable_composition: enabled with min_hits = %u already, not %u", ss.comp_min_hits, min_hits);
+    }
+    SKXCHK(stats_can_enable(st, "skx_stream_enable_composition"));
+    const skx_ref* ref = st->ref;
+    if (ref->n_species > 64)
+        return fail(SKX_ERR_UNSUPPORTED, "skx_stream_enable_composition: %u species (a species mask holds 64)", ref->n_species);
+    SKXCHK(ref_species_mask(ref, st->hs));
+    const size_t n_ctr = (size_t)2 * ref->n_species + 2u;
+    const u32 tmp_n = std::max(st->pcap, std::max(st->qcap, st->qcap_max));  // (positions in a pass's Q, as d_dep_tmp)
+    u64 *ctr = nullptr, *qmask = nullptr;
+    hipError_t e = skx::comp_count_prepare(ref->n_species);  // (a kernel that cannot get its LDS fails here, not in a push)
+    if (e == hipSuccess) e = hipMalloc(&ctr, n_ctr * 8);
+    if (e == hipSuccess) e = hipMalloc(&qmask, (size_t)tmp_n * 8);
+    if (e == hipSuccess) e = hipMemset(ctr, 0, n_ctr * 8);
+    if (e != hipSuccess) {  // (all or nothing: the stream is left as it was; the reference keeps its masks)
+        (void)hipFree(ctr); (void)hipFree(qmask);
+        (void)hipGetLastError();
+        return fail(SKX_ERR_HIP, "skx_stream_enable_composition: %s", hipGetErrorString(e));
+    }
+    ss.d_comp_qmask = qmask; ss.comp_min_hits = min_hits;
+    ss.d_comp = ctr;
+    return SKX_OK;
+}
+SKX_API int skx_stream_composition(skx_stream* st, uint64_t* reads, uint64_t* pairs) {
+    if (!st) return fail(SKX_ERR_INVALID, "NULL stream");
+    if (!st->stats.d_comp) return fail(SKX_ERR_INVALID, "skx_stream_composition: composition was never enabled on this stream");
+    SKXCHK(use_device(st->device));
+    SKXCHK(flush_pending(st));
+    const u32 n_sp = st->ref->n_species;
+    hipError_t e = hipSuccess;  // (behind the counts of every pass queued so far; the caller's arrays are only borrowed until the wait)
+    if (reads) e = hipMemcpyAsync(reads, st->stats.d_comp, ((size_t)n_sp + 2u) * 8, hipMemcpyDeviceToHost, st->hs);
+    if (e == hipSuccess && pairs) e = hipMemcpyAsync(pairs, st->stats.d_comp + n_sp + 2u, (size_t)n_sp * 8, hipMemcpyDeviceToHost, st->hs);
+    const hipError_t e2 = hipStreamSynchronize(st->hs);
+    if (e == hipSuccess) e = e2;
+    if (e != hipSuccess) return fail(SKX_ERR_HIP, "skx_stream_composition: %s", hipGetErrorString(e));
+    return SKX_OK;
 }
 
 // ------------------------------------------------------------------ the queries of both statistics

@@ -4747,6 +4747,122 @@ __global__ __launch_bounds__(256) void depth_import_kernel(const u64* __restrict
 }
 
 // =====================================================================================
+// composition of a stream: which species does every read belong to (skx_stream_enable_composition)
+// =====================================================================================
+// The reference side, once per reference: spmask[slot] = bit sp for every species with a genome that holds key[slot] (u64: up to 64
+// species, the species call's limit).  One walk over stat_walk's traversal -- lane = genome of an aligned 64-genome group, stat_probe4 --
+// and the wave offers its species' bit for the slots its lanes find.  The species of a padded genome is the species of its rank group
+// (sp.of_grp): a species is padded to whole rank groups of 512 genomes, so the 64 lanes of a wave -- an aligned 64-genome group -- are
+// one species and carry ONE bit.  The lanes of a wave mostly meet on one slot: one atomicOr per DISTINCT slot per wave, sent by the
+// lowest of the lanes there (winner_offer's ballot loop); a lane whose plain load of spmask[slot] holds the bit already has nothing to
+// send -- the bits only get set, so a stale load only costs an atomic.  Padding (>= kEmpty) is never probed and the lifted hashes are
+// not in the matrix: they count for nobody.  spmask zero on entry.
+__device__ __forceinline__ void species_offer(unsigned long long* spmask, u32 at, u64 bit) {
+    if (at != kSlotNone && (spmask[at] & bit)) at = kSlotNone;
+    u64 todo = __ballot(at != kSlotNone);
+    const u64 me = 1ull << (threadIdx.x & 63u);
+    while (todo) {
+        const u32 first = __shfl(at, __ffsll((long long)todo) - 1);
+        const u64 same = __ballot(at == first) & todo;
+        if ((same & (0ull - same)) == me) atomicOr(&spmask[first], (unsigned long long)bit);  // (bit is the wave's)
+        todo &= ~same;
+    }
+}
+__global__ __launch_bounds__(256) void species_mask_kernel(const u64* __restrict__ mat, u32 s, const u64* __restrict__ key, u32 mask,
+                                                           Species sp, unsigned long long* spmask) {
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    const u32 p = blockIdx.x * 64u + lane;
+    const u64* col = mat + (size_t)(p / kTileGenomes) * s * kTileGenomes + p % kTileGenomes;
+    const u32 r0 = blockIdx.y * kCovRanks, r1 = min(s, r0 + kCovRanks);
+    const u64 bit = 1ull << sp.of_grp[blockIdx.x / kRankWords];  // (the group's rank group: 64 | 512)
+    for (u32 r = r0 + wv; r < r1; r += 16u) {  // (r, r1 are the wave's: the ballots see all 64 lanes)
+        u32 sl[4];
+        stat_probe4(col, r, r1, key, mask, sl);
+#pragma unroll
+        for (u32 j = 0; j < 4u; ++j) species_offer(spmask, sl[j], bit);
+    }
+}
+// The stream side, two kernels behind a pass's pair_q_kernel (beside depth's, same inputs):
+//   comp_qmask_kernel  one lane per distinct hash of the pass: qmask[i] = spmask[slot of Q[i]] (stat_index; spmask == NULL: a reference
+//                      of one species, a found slot has mask 1), 0 for a hash nobody holds and for the lifted values
+//   comp_count_kernel  one launch per batch of the pass, one THREAD per read (a read has a handful of pairs: dict_insert_kernel; the
+//                      reads with more than kCompLong pairs are taken by their wave, a pair per lane, into the same counters).  The
+//                      thread finds every pair's position in Q (depth_count_kernel's search), takes qmask there and adds one to
+//                      cnt[species][thread] for every set bit -- LDS, the thread on the bank: no conflicts whatever species the lanes touch
+//                      (depth_select_kernel's hist), n_sp rows only (dynamic LDS).  A read's sketch holds a hash once, so cnt = hits.
+//                      Then best = max hits: below min_hits -> unclassified (class n_sp + 1), attained by one species -> that species,
+//                      by several -> ambiguous (class n_sp).  The block adds up its classes (ds atomics) and the species' hits (a wave
+//                      per species) and sends one 64-bit atomicAdd per non-zero counter: reads [n_sp + 2], pairs [n_sp].
+constexpr u32 kCompLong = 16;  // pairs above which a read is counted by its wave and not by its thread
+__global__ __launch_bounds__(256) void comp_qmask_kernel(const u64* __restrict__ q, const u32* __restrict__ n_q, u32 q_bound,
+                                                         const u32* __restrict__ qinfo, const unsigned long long* __restrict__ spmask,
+                                                         u32 kt_slots, u64* __restrict__ qmask) {
+    const u32 nq = min(*n_q, q_bound), i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= nq) return;
+    const u32 at = stat_index(q[i], qinfo, i, kt_slots);
+    qmask[i] = at < kt_slots ? (spmask ? spmask[at] : 1ull) : 0ull;  // (kSlotNone and the lifted hashes' indices lie beyond the slots)
+}
+__global__ __launch_bounds__(256) void comp_count_kernel(const u64* __restrict__ pair_h, const u32* __restrict__ poff, u32 p_base,
+                                                         u32 n_reads, const u64* __restrict__ q, const u32* __restrict__ n_q, u32 q_bound,
+                                                         const u32* __restrict__ bbase, const u32* __restrict__ btot, u32 bshift,
+                                                         const u64* __restrict__ qmask, u32 n_sp, u32 min_hits,
+                                                         unsigned long long* __restrict__ reads, unsigned long long* __restrict__ pairs) {
+    extern __shared__ u32 comp_lds[];  // cnt [n_sp][256], cls [n_sp + 2]
+    u32* cnt = comp_lds + threadIdx.x;
+    u32* cls = comp_lds + n_sp * 256u;
+    const u32 r = blockIdx.x * 256u + threadIdx.x, nq = min(*n_q, q_bound);
+    for (u32 sp = 0; sp < n_sp; ++sp) cnt[sp * 256u] = 0;
+    if (threadIdx.x < n_sp + 2u) cls[threadIdx.x] = 0;
+    __syncthreads();
+    u32 a = 0, b = 0;
+    if (r < n_reads) { a = poff[r] - p_base; b = poff[r + 1] - p_base; }
+    // the species mask of pair j (0: nobody's, or a lifted value)
+    auto mask_of = [&](u32 j) -> u64 {
+        const u64 h = pair_h[j];
+        if (h >= kEmpty) return 0ull;
+        const u32 bk = dict_bucket(h, bshift);
+        u32 at = btot[bk >> 10] + bbase[bk];
+        while (at < nq && q[at] < h) ++at;
+        return (at < nq && q[at] == h) ? qmask[at] : 0ull;
+    };
+    const bool is_long = b - a > kCompLong;
+    if (!is_long)
+        for (u32 j = a; j < b; ++j)
+            for (u64 m = mask_of(j); m; m &= m - 1ull) cnt[(u32)(__ffsll((long long)m) - 1) * 256u] += 1u;
+    // a long read (a mixed-length stream has reads of tens of kb beside the short ones) would keep its wave waiting for one lane:
+    // the wave takes its long reads one after the other, a pair per lane, into the owner's column (ds atomics: lanes meet there)
+    const u32 lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    for (u64 todo = __ballot(is_long); todo; todo &= todo - 1ull) {
+        const int src = __ffsll((long long)todo) - 1;
+        const u32 la = __shfl(a, src), lb = __shfl(b, src);
+        u32* col = comp_lds + wv * 64u + (u32)src;
+        for (u32 j = la + lane; j < lb; j += 64u)
+            for (u64 m = mask_of(j); m; m &= m - 1ull) atomicAdd(&col[(u32)(__ffsll((long long)m) - 1) * 256u], 1u);
+    }
+    __syncthreads();  // (a long read's counters come from its whole wave)
+    if (r < n_reads) {
+        u32 best = 0, arg = 0, n_best = 0;
+        for (u32 sp = 0; sp < n_sp; ++sp) {
+            const u32 c = cnt[sp * 256u];
+            if (c > best) { best = c; arg = sp; n_best = 1; }
+            else if (c == best) ++n_best;
+        }
+        atomicAdd(&cls[best < min_hits ? n_sp + 1u : n_best == 1u ? arg : n_sp], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < n_sp + 2u && cls[threadIdx.x]) atomicAdd(&reads[threadIdx.x], (unsigned long long)cls[threadIdx.x]);
+    for (u32 sp = wv; sp < n_sp; sp += 4u) {
+        const u32* row = comp_lds + sp * 256u;
+        u32 t = row[lane] + row[lane + 64u] + row[lane + 128u] + row[lane + 192u];
+#pragma unroll
+        for (u32 d = 32u; d; d >>= 1) t += (u32)__shfl_xor((int)t, (int)d);
+        if (lane == 0 && t) atomicAdd(&pairs[sp], (unsigned long long)t);
+    }
+}
+// reads without a pair bring no launch of the above: *ctr += n
+__global__ void comp_add_kernel(unsigned long long* __restrict__ ctr, u32 n) { atomicAdd(ctr, (unsigned long long)n); }
+
+// =====================================================================================
 // the table without the ranking, and the genomes a batch's ranking has to look at (round 5)
 // =====================================================================================
 // Rounds 1-4 took the running table out of the ranking chain: per-segment increments, chunk sums, prefixes -- every pair's 64-byte
@@ -6672,6 +6788,34 @@ void launch_depth_walk(hipStream_t st, const u64* mat, u32 s, const u32* groups,
     hipLaunchKernelGGL(depth_walk_kernel, dim3(n_groups, cdiv(s, kCovRanks)), dim3(256), 0, st, mat, s, groups, g0, key, mask, depth, exc_g,
                        exc_h, n_exc, covered, total, vmax, vals);
     hipLaunchKernelGGL(depth_select_kernel, dim3(n_groups), dim3(256), 0, st, vals, s, groups, g0, covered, vmax, median);
+}
+static u32 comp_count_lds(u32 n_sp) { return (n_sp * 256u + n_sp + 2u) * 4u; }  // cnt [n_sp][256] + cls [n_sp + 2]
+void launch_species_mask(hipStream_t st, const u64* mat, u32 s, u32 n_groups, const u64* key, u32 mask, Species sp, u64* spmask) {
+    if (n_groups == 0 || s == 0) return;
+    hipLaunchKernelGGL(species_mask_kernel, dim3(n_groups, cdiv(s, kCovRanks)), dim3(256), 0, st, mat, s, key, mask, sp,
+                       (unsigned long long*)spmask);
+}
+void launch_comp_qmask(hipStream_t st, const u64* q, const u32* n_q, u32 q_bound, const u32* qinfo, const u64* spmask, u32 kt_slots,
+                       u64* qmask) {
+    if (q_bound == 0) return;
+    hipLaunchKernelGGL(comp_qmask_kernel, dim3(cdiv(q_bound, 256)), dim3(256), 0, st, q, n_q, q_bound, qinfo,
+                       (const unsigned long long*)spmask, kt_slots, qmask);
+}
+hipError_t comp_count_prepare(u32 n_sp) {
+    const u32 lds = comp_count_lds(n_sp);
+    if (lds <= 32768u) return hipSuccess;  // (up to 31 species: what a kernel may take of the LDS without asking)
+    return hipFuncSetAttribute((const void*)comp_count_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+void launch_comp_count(hipStream_t st, const u64* pair_h, const u32* poff, u32 p_base, u32 n_reads, const u64* q, const u32* n_q,
+                             u32 q_bound, const u32* bbase, const u32* btot, u64 max_ref, const u64* qmask, u32 n_sp, u32 min_hits, u64* reads,
+                             u64* pairs) {
+    if (n_reads == 0) return;
+    hipLaunchKernelGGL(comp_count_kernel, dim3(cdiv(n_reads, 256)), dim3(256), comp_count_lds(n_sp), st, pair_h, poff, p_base, n_reads, q, n_q, q_bound, bbase,
+                       btot, dict_bshift(max_ref), qmask, n_sp, min_hits, (unsigned long long*)reads, (unsigned long long*)pairs);
+}
+void launch_comp_add(hipStream_t st, u64* ctr, u32 n) {
+    if (n == 0) return;
+    hipLaunchKernelGGL(comp_add_kernel, dim3(1), dim3(1), 0, st, (unsigned long long*)ctr, n);
 }
 void launch_depth_export(hipStream_t st, const u64* key, const u32* depth, u64 kt_slots, u64* hashes, u32* counts, u64 cap,
                          unsigned long long* n) {

@@ -441,6 +441,21 @@ void launch_depth_export(hipStream_t st, const u64* key, const u32* depth, u64 k
 // depth[hash's index] = sat(+ counts[i]), its seen bit set where counts[i] > 0; *n_unknown += entries that are no key (zero on entry)
 void launch_depth_import(hipStream_t st, const u64* hashes, const u32* counts, u64 n, const u64* key, u32 mask, u32* depth, u32* seen,
                          unsigned long long* n_unknown);
+// ---- composition of a stream (skx_kernels.hip, "composition of a stream").  spmask: one u64 per key-table slot, bit sp = some genome of
+// species sp holds the key; zero on entry of launch_species_mask, which walks the whole table (groups 0 .. n_groups - 1).
+void launch_species_mask(hipStream_t st, const u64* mat, u32 s, u32 n_groups, const u64* key, u32 mask, Species sp, u64* spmask);
+// behind launch_pair_q of the same pass, same stream (inputs as launch_depth_mark's): qmask [>= q_bound] = the species mask of every distinct
+// hash of the pass (spmask == NULL: one species, a found slot has mask 1) ...
+void launch_comp_qmask(hipStream_t st, const u64* q, const u32* n_q, u32 q_bound, const u32* qinfo, const u64* spmask, u32 kt_slots,
+                       u64* qmask);
+// ... and, per batch of the pass (pair_h: its part of the pass's pair hashes; read i < n_reads has the pairs [poff[i] - p_base,
+// poff[i + 1] - p_base) of it): reads [n_sp + 2] += its reads per class, pairs [n_sp] += their hits per species.  comp_count_prepare:
+// once per device before the first launch with that many species (above 31 the kernel has to ask for its LDS)
+hipError_t comp_count_prepare(u32 n_sp);
+void launch_comp_count(hipStream_t st, const u64* pair_h, const u32* poff, u32 p_base, u32 n_reads, const u64* q, const u32* n_q,
+                             u32 q_bound, const u32* bbase, const u32* btot, u64 max_ref, const u64* qmask, u32 n_sp, u32 min_hits, u64* reads,
+                             u64* pairs);
+void launch_comp_add(hipStream_t st, u64* ctr, u32 n);  // *ctr += n
 
 // ---- pooled sketches (skx_kernels.hip, "pooled sketches"): the bottom-s distinct hashes of the union of a group's rows
 // One round of the segmented merge tree: items[i] = {left row, partner row or 0xFFFFFFFF (no partner: the row is copied)}; rows are

@@ -88,6 +88,9 @@ extern "C" int skx_stream_depth_rows(skx_stream* st, const uint32_t* genomes, ui
     __attribute__((weak));
 // ... and the breadth with every seen hash credited to one sketch (`screen --winner-take-all`): the winner is a property of each hash
 extern "C" int skx_stream_winners(skx_stream* st, uint32_t* covered, uint32_t* won) __attribute__((weak));
+// ... and what the read set is made of (`composition`): every read is classified on the device, beside the stream
+extern "C" int skx_stream_enable_composition(skx_stream* st, uint32_t min_hits) __attribute__((weak));
+extern "C" int skx_stream_composition(skx_stream* st, uint64_t* reads, uint64_t* pairs) __attribute__((weak));
 
 namespace sketchy {
 
@@ -420,6 +423,78 @@ class Sketchy {
                 out << "\t" << buf;
             }
             if (with_geno) out << "\t" << join_tab(geno.map.at(sketches[g].name));
+            out << "\n";
+        }
+    }
+
+    // `composition` (not in the reference): what the read set is made of.  The references -- one species each, named by the file without
+    // directory and .msh as in `predict` with several -r -- are resident together, all reads go through one table-only stream with
+    // composition enabled (skx_stream_enable_composition), and every read is one species' (the one its own sketch shares the most hashes
+    // with, at least min_hits), ambiguous (several species tie) or unclassified.  One line per reference -- species reads fraction pairs,
+    // fraction = reads / all reads, pairs = hashes the reads shared with the species -- then the lines ambiguous and unclassified.
+    // The files must agree in k-mer size and seed; the reads are sketched with the size of the first file's first sketch.
+    void composition(const std::string& fastx, const std::vector<std::string>& references, uint32_t min_hits, size_t limit, bool header,
+                     std::ostream& out) {
+        // (there is no host route to the numbers: a library without the entry points ends here, before anything is read)
+        auto need = [](bool have, const char* name) {
+            if (!have) throw UsageError(std::string("composition needs ") + name + ", which the loaded libsketchy_hip does not export");
+        };
+        need(skx_stream_enable_composition != nullptr, "skx_stream_enable_composition");
+        need(skx_stream_composition != nullptr, "skx_stream_composition");
+        need(skx_ref_create_multi != nullptr, "skx_ref_create_multi");
+        if (references.size() > SKX_MAX_SPECIES) throw UsageError("at most " + std::to_string(SKX_MAX_SPECIES) + " references can be resident together");
+        std::vector<std::string> names;
+        std::vector<std::vector<Sketch>> all;
+        for (const auto& path : references) {
+            auto sketches = read_sketch(path);
+            if (sketches.empty()) throw SketchyError("reference sketch file " + path + " holds no sketches");
+            const auto slash = path.find_last_of('/');
+            std::string name = slash == std::string::npos ? path : path.substr(slash + 1);
+            if (name.size() > 4 && name.compare(name.size() - 4, 4, ".msh") == 0) name.resize(name.size() - 4);
+            names.push_back(name);
+            const Sketch &a = all.empty() ? sketches[0] : all[0][0], &b = sketches[0];
+            if (a.kmer_length != b.kmer_length || a.hash_seed != b.hash_seed)
+                throw UsageError("references " + references[0] + " and " + path + " do not agree in k-mer size and seed (" + std::to_string(a.kmer_length) +
+                                 "/" + std::to_string(a.hash_seed) + " and " + std::to_string(b.kmer_length) + "/" + std::to_string(b.hash_seed) + ")");
+            all.push_back(std::move(sketches));
+        }
+        Ref ref(all, device_);
+        const size_t n_sp = all.size();
+        const uint64_t max_bases = 1ull << 28;
+        skx_stream* st = nullptr;
+        hip_check(skx_stream_create(&st, ref.h, 0, (uint32_t)batch_, max_bases), "stream");
+        std::vector<uint64_t> reads(n_sp + 2), pairs(n_sp);
+        try {
+            hip_check(skx_stream_enable_composition(st, min_hits), "composition");
+            FastxReader reader(fastx);
+            Batch b; std::string seq;
+            size_t n = 0;
+            auto flush = [&]() {
+                if (b.n() == 0) return;
+                hip_check(skx_stream_push(st, b.bases.data(), b.offsets.data(), (uint32_t)b.n(), nullptr, nullptr, nullptr, nullptr, nullptr), "composition");
+                b.clear();
+            };
+            while (reader.next(seq)) {
+                if (b.n() && b.bases.size() + seq.size() > max_bases) flush();
+                b.add(seq); ++n;
+                if (b.n() == batch_) flush();
+                if (n == limit) break;
+            }
+            flush();
+            hip_check(skx_stream_composition(st, reads.data(), pairs.data()), "composition");
+        } catch (...) {
+            skx_stream_destroy(st);
+            throw;
+        }
+        skx_stream_destroy(st);
+        uint64_t total = 0;
+        for (uint64_t r : reads) total += r;
+        if (header) out << "species\treads\tfraction\tpairs\n";
+        char buf[32];
+        for (size_t i = 0; i < n_sp + 2; ++i) {
+            std::snprintf(buf, sizeof buf, "%.6f", total ? (double)reads[i] / (double)total : 0.0);
+            out << (i < n_sp ? names[i] : i == n_sp ? std::string("ambiguous") : std::string("unclassified")) << "\t" << reads[i] << "\t" << buf << "\t";
+            if (i < n_sp) out << pairs[i]; else out << "-";
             out << "\n";
         }
     }
@@ -1487,6 +1562,10 @@ static void usage() {
                  "                    -w / --winner-take-all: every seen hash is credited to ONE sketch, the best of those that hold it (by\n"
                  "                    containment, then covered, then file order): the TOP sketches by won / sketch_size, the columns won and\n"
                  "                    winner_containment behind shared_hashes, the identity from the winner containment)\n"
+                 "sketchy-hip composition -r A.msh [B.msh ...] -i READS.fx[.gz] [-m MIN_HITS=1] [-l LIMIT] [-H] [--device N]\n"
+                 "                    (what the read set is made of: every reference is one species, named by its file without .msh; a read is the\n"
+                 "                    species' whose sketches share the most hashes with the read's own sketch, at least MIN_HITS -- species reads\n"
+                 "                    fraction pairs, one line per reference; then ambiguous (several species tie) and unclassified)\n"
                  "sketchy-hip shared  -r REF.msh -q QUERY.msh\n"
                  "sketchy-hip info    -i SKETCH.msh [-p]\n"
                  "sketchy-hip check   -r REF.msh -g GENO.tsv\n");
@@ -1513,7 +1592,7 @@ int main(int argc, char** argv) {
         if (longnames.count(a)) a = longnames.at(a);
         // (predict: a lone "-" is a path -- stdin)
         if (many_inputs && a == "-i") { while (i + 1 < argc && (argv[i + 1][0] != '-' || (!is_sketch && !argv[i + 1][1]))) inputs.push_back(argv[++i]); continue; }
-        if (cmd == "predict" && (a == "-r" || a == "-g")) {
+        if ((cmd == "predict" && (a == "-r" || a == "-g")) || (cmd == "composition" && a == "-r")) {
             auto& list = a == "-r" ? references : tables;
             if (i + 1 >= argc) { usage(); return 2; }
             while (i + 1 < argc && argv[i + 1][0] != '-') list.push_back(argv[++i]);
@@ -1582,6 +1661,11 @@ int main(int argc, char** argv) {
             if (top < 1) { std::fprintf(stderr, "Error: --top must be at least 1\n"); return 2; }
             app.screen(opt["-i"], opt["-r"], opt.count("-g") ? opt["-g"] : std::string(), (size_t)top, (size_t)std::max(0L, limit), flag["-H"], std::cout,
                        flag["--depth"], flag["--identity"], flag["--winner-take-all"]);
+        } else if (cmd == "composition") {
+            if (references.empty() || !opt.count("-i")) { usage(); return 2; }
+            const long min_hits = opt.count("-m") ? std::atol(opt["-m"].c_str()) : 1, limit = opt.count("-l") ? std::atol(opt["-l"].c_str()) : 0;
+            if (min_hits < 1 || min_hits > 0xFFFFFFFFL) { std::fprintf(stderr, "Error: -m (the hits that make a read a species') must be at least 1\n"); return 2; }
+            app.composition(opt["-i"], references, (uint32_t)min_hits, (size_t)std::max(0L, limit), flag["-H"], std::cout);
         } else if (cmd == "shared") {
             if (!opt.count("-r") || !opt.count("-q")) { usage(); return 2; }
             app.shared(opt["-r"], opt["-q"], std::cout);
